@@ -21,6 +21,13 @@ devices; the merge goes through the host).
 Synthetic data: roster and streams come from the on-device counter RNG
 (random-init ratings), generated before the timed region like a prefetched
 data loader; the timed region contains all rating work of every step.
+
+A plain run does only what the headline figure needs: set up, warm up, time the
+steps, print the JSON line.  ``--full`` adds the untimed measurement that used to
+follow every N > 1 run (the sweep-DP error against exact sequential rating);
+``--check`` and ``--verify`` (device vs fp64 host mirror) are asked for by name;
+``--dump-outputs DIR`` writes the last timed step's results as ``.npy`` files, so
+that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -59,6 +66,19 @@ def parse(argv=None):
     ap.add_argument("--team-size", type=int, default=3)
     ap.add_argument("--ring", type=int, default=4, help="distinct pre-generated windows per rank")
     ap.add_argument("--seed", type=int, default=2024)
+    ap.add_argument("--full", action="store_true",
+                    help="after timing, also run what the headline figure does not need and no option of "
+                         "its own asks for: for N > 1 the sweep-DP error against exact sequential rating "
+                         "(--accuracy).  Off by default: a plain run sets up, warms up, times the steps and "
+                         "prints the JSON line; --check and --verify stay options of their own")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what its last timed step computed to "
+                         "DIR/<name>.npy (float32): the last window's output records field by field "
+                         "(quality, status, s_mu, s_sig, delta, m_mu, m_sig; config 4: telemetry_stats) "
+                         "for a fixed seeded sample of its matches (record_rows), and the roster's "
+                         "(mu, sigma) granules for a fixed seeded sample of players (roster_rows); NULL "
+                         "(NaN) entries are written as 0 and marked with 1 in <name>_null.npy.  The "
+                         "same arguments give the same inputs and the same samples in every run")
     ap.add_argument("--check", action="store_true", help="also validate statuses after timing")
     ap.add_argument("--verify", action="store_true",
                     help="after timing, rate window 0 again on the device and on the fp64 host "
@@ -99,7 +119,7 @@ def parse(argv=None):
                          "0.9897 at N = k = 4 but 0.9971 at k = 8, 0.9884 at N = k = 8 but 0.9965 at k = 16 "
                          "(profiles/r3/merges_vs_ranks_5v5.log)")
     ap.add_argument("--accuracy", type=int, default=1,
-                    help="N > 1: after timing, rank 0 measures the sweep-DP error of this run's "
+                    help="N > 1 with --full: after timing, rank 0 measures the sweep-DP error of this run's "
                          "configuration against the exact sequential rating (parallel/accuracy.py, "
                          "N ranks simulated on its GPU) and reports it in the JSON line (0 = skip)")
     ap.add_argument("--emulate-allreduce", default=None, metavar="N:GBps[:us]",
@@ -115,6 +135,8 @@ def parse(argv=None):
                     help="causal sweeps per window (N > 1): 1 = one merge (approximate); "
                          "N = exact sequential semantics (parallel/sweep.py)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config == 3:
         args.team_size = 5
         if args.matches_per_gpu == 10_000_000:
@@ -167,6 +189,54 @@ def shared_card_blocks(world: int, ngpu: int, backend: str) -> int:
     if backend == "nccl" or not ngpu or world <= ngpu:
         return 0
     return max(16, 512 // -(-world // ngpu))
+
+
+DUMP_ROWS = 1 << 16        # sampled matches / players per dumped array
+DUMP_MAX_BYTES = 64 << 20  # all files of one dump together
+
+
+def _sample_rows(n: int, seed: int) -> torch.Tensor:
+    """Sorted row numbers of the dump: all ``n`` rows, or DUMP_ROWS of them drawn
+    without replacement by a CPU generator seeded with ``seed``."""
+    if n <= DUMP_ROWS:
+        return torch.arange(n, dtype=torch.int64)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    return torch.randperm(n, generator=g)[:DUMP_ROWS].sort().values
+
+
+def dump_outputs(path: str, out, roster, stats, seed: int) -> dict:
+    """Write what the last timed step computed -- ``out`` (the RateResult of its last
+    window), the roster's (mu, sigma) granules and, for config 4, the telemetry
+    ``stats`` -- to ``path/<name>.npy`` as float32, sampled by row (``record_rows`` /
+    ``roster_rows``, float64 row numbers).  The files hold finite numbers only, so that
+    any element-wise comparison of two dumps works: an array with NULL entries (NaN: an
+    unrated track, the records of an AFK match) is written with 0 in their place, and
+    ``<name>_null.npy`` marks them with 1.  Returns {name: shape}."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    rows = _sample_rows(int(out.status.shape[0]), seed + 101)
+    players = _sample_rows(roster.num_players, seed + 102)
+    arrays = {"record_rows": rows.double(), "roster_rows": players.double()}
+    ridx = rows.to(out.status.device)
+    for name in out.FIELDS:
+        arrays[name] = getattr(out, name).index_select(0, ridx).float()
+    if stats is not None:
+        arrays["telemetry_stats"] = stats.index_select(0, ridx).float()
+    state = roster.state.index_select(0, players.to(roster.state.device))
+    arrays["roster_mu"] = state[:, 0::4].float()      # granule g: shared track, then the modes
+    arrays["roster_sigma"] = state[:, 2::4].float()
+    arrays = {k: np.ascontiguousarray(v.cpu().numpy()) for k, v in arrays.items()}
+    for name in [k for k in arrays if k not in ("record_rows", "roster_rows", "status")]:
+        null = np.isnan(arrays[name])
+        arrays[name + "_null"] = null.astype(np.float32)
+        arrays[name] = np.where(null, np.float32(0), arrays[name])
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "dump of %d bytes" % total
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def _free_port() -> int:
@@ -438,6 +508,8 @@ def main(argv=None) -> int:
     flags = rater.sticky_flags(dev).cpu()
     if int(flags.sum()):
         raise RuntimeError("dataflow error flags set during the benchmark: %s" % flags.tolist())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[(total_windows - 1) % len(outs)], roster, stats, args.seed)
     if args.check:
         out = outs[(total_windows - 1) % len(outs)]
         counts = out.status_counts()
@@ -453,7 +525,7 @@ def main(argv=None) -> int:
         if tele is not None:
             verify["note"] = "rating only (telemetry is checked by tests/test_telemetry.py)"
     accuracy = None
-    if world > 1 and args.accuracy and rank == 0 and args.config != 4:
+    if args.full and world > 1 and args.accuracy and rank == 0 and args.config != 4:
         # untimed: the error this run's settings leave against the exact sequential
         # result -- the same N, roster, slice length, merges, sweeps and message dtype,
         # the N ranks simulated with the same kernels on this GPU (parallel/accuracy.py)
@@ -511,6 +583,7 @@ def main(argv=None) -> int:
             # where the next window's prepass ran (runtime/engine.py placement)
             "schedule": {"executor_workgroups": pipe.grid,
                          "prepass": ("serial" if pipe.serial else "rating tail %.2f" % pipe.tail)},
+            "full": bool(args.full),
             "verify": verify,
             "accuracy": accuracy,
             "rccl_world": dist.get_world_size() if world > 1 else None,

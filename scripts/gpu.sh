@@ -90,10 +90,10 @@ for task in "$@"; do
       run bench/skew3 900 $PY bench.py --skew 3 --steps 2 --warmup 1 --check
       ;;
     dp)
-      run dp/gloo2 600 env ANA_DIST_BACKEND=gloo $PY bench.py --gpus 2 --steps 5 --warmup 2
-      run dp/gloo4 900 env ANA_DIST_BACKEND=gloo $PY bench.py --gpus 4 --steps 3 --warmup 1
-      run dp/gloo8 900 env ANA_DIST_BACKEND=gloo $PY bench.py --gpus 8 --steps 2 --warmup 1
-      run dp/gloo2_sweeps2 600 env ANA_DIST_BACKEND=gloo $PY bench.py --gpus 2 --steps 3 --warmup 1 --sweeps 2
+      run dp/gloo2 600 env ANA_DIST_BACKEND=gloo $PY bench.py --gpus 2 --steps 5 --warmup 2 --full
+      run dp/gloo4 900 env ANA_DIST_BACKEND=gloo $PY bench.py --gpus 4 --steps 3 --warmup 1 --full
+      run dp/gloo8 900 env ANA_DIST_BACKEND=gloo $PY bench.py --gpus 8 --steps 2 --warmup 1 --full
+      run dp/gloo2_sweeps2 600 env ANA_DIST_BACKEND=gloo $PY bench.py --gpus 2 --steps 3 --warmup 1 --sweeps 2 --full
       ;;
     accuracy)
       run accuracy/dp8 900 $PY -m analyzer_amd.parallel.accuracy --device cuda --ranks 8 \
@@ -344,8 +344,8 @@ print("2 ranks | resumed from window", int(res["resumed_from_window"]), "| roste
 EOF2
       ;;
     dpconf)  # gloo rehearsals of the other DP configs: 5v5 (config 3, k = 2N) and the 10M-player re-rate (config 5)
-      run dpconf/c3_gloo4 900 env ANA_DIST_BACKEND=gloo $PY bench.py --config 3 --gpus 4 --steps 1 --warmup 1
-      run dpconf/c5_gloo2 900 env ANA_DIST_BACKEND=gloo $PY bench.py --config 5 --gpus 2 --steps 1 --warmup 1
+      run dpconf/c3_gloo4 900 env ANA_DIST_BACKEND=gloo $PY bench.py --config 3 --gpus 4 --steps 1 --warmup 1 --full
+      run dpconf/c5_gloo2 900 env ANA_DIST_BACKEND=gloo $PY bench.py --config 5 --gpus 2 --steps 1 --warmup 1 --full
       ;;
     project)  # N-GPU step projection on one GPU: k = N forced merges with the all-reduce stand-in
               # (N ranks, BW GB/s bus bandwidth), N = 2 / 4 / 8 at 300 GB/s, N = 8 at 150 / 600 GB/s

@@ -91,14 +91,81 @@ def test_shared_card_blocks():
     assert bench.shared_card_blocks(64, 1, "gloo") == 16
 
 
-@pytest.mark.parametrize("n", [2, 4, 8])
-def test_multi_rank_json_contract_on_cpu(tmp_path, n):
-    """The N > 1 path of the driver contract end to end on the CPU (``--device cpu``:
-    host mirror, gloo): bench.py spawns its own N ranks (127.0.0.1 rendezvous), runs
-    one-prepass-per-step DP steps with a merge after each of k = N windows, and rank 0
-    prints ONE JSON line with the N > 1 keys -- the rank count, the merge split with the
-    prepass placement, the accuracy block with the per-participant record errors and
-    the merge decodes' clamp count."""
+def _run_on_cpu(capsys, *extra):
+    import json
+
+    capsys.readouterr()
+    assert bench.main(["--device", "cpu", "--gpus", "1", "--players", "3000", "--matches-per-gpu", "5000",
+                       "--steps", "3", "--warmup", "1"] + list(extra)) == 0
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_plain_run_is_lean_and_full_adds_the_checks(capsys):
+    """A plain run times its steps and prints the line: no status check, no fp64
+    verification, no accuracy pass.  --full (the N > 1 accuracy pass, see
+    test_multi_rank_json_contract_on_cpu) changes nothing else on one rank; --verify
+    stays an option of its own."""
+    a = bench.parse([])
+    assert not (a.full or a.check or a.verify or a.dump_outputs)
+    j = _run_on_cpu(capsys)
+    assert j["full"] is False and j["verify"] is None and j["accuracy"] is None
+    assert (j["steps"], j["warmup"]) == (3, 1) and j["ms_per_step"] > 0
+    assert j["value"] == pytest.approx(5000 / (j["ms_per_step"] / 1000.0))
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert key in j
+    j = _run_on_cpu(capsys, "--full", "--verify")
+    assert j["full"] is True and j["accuracy"] is None
+    assert j["verify"]["status_mismatch"] == 0 and j["verify"]["matches"] == 5000
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_writes_the_last_steps_results(tmp_path, capsys):
+    """--dump-outputs: finite float arrays of the last timed step's records and roster
+    (NULL = NaN entries as 0, marked in <name>_null), the same from run to run, and what
+    rating the same windows by hand gives."""
+    import numpy as np
+    import torch
+
+    from analyzer_amd.ops.rate import BatchRater, RateResult
+    from analyzer_amd.ops.synth import RosterSpec, StreamSpec, make_roster, make_stream
+
+    a, b = tmp_path / "a", tmp_path / "b"
+    _run_on_cpu(capsys, "--dump-outputs", str(a))
+    _run_on_cpu(capsys, "--dump-outputs", str(b))
+    names = sorted(p.name for p in a.iterdir())
+    values = tuple(f for f in RateResult.FIELDS if f != "status") + ("roster_mu", "roster_sigma")
+    assert names == sorted(n + ".npy" for n in values + tuple(v + "_null" for v in values)
+                           + ("status", "record_rows", "roster_rows"))
+    got = {n[:-4]: np.load(str(a / n)) for n in names}
+    assert sum(v.nbytes for v in got.values()) <= bench.DUMP_MAX_BYTES
+    for n in names:
+        assert got[n[:-4]].dtype in (np.float32, np.float64) and np.isfinite(got[n[:-4]]).all(), n
+        assert np.array_equal(got[n[:-4]], np.load(str(b / n)), equal_nan=True), n
+    assert got["s_mu"].shape == (5000, 6) and got["roster_mu"].shape == (3000, 8)
+    assert np.array_equal(got["record_rows"], np.arange(5000))
+    # 1 warm-up + 3 timed steps over a ring of 4 windows: the last step rates window 3
+    roster = make_roster(RosterSpec(num_players=3000, seed=2024))
+    spec = StreamSpec(team_size=3, seed=2025)
+    rater = BatchRater()
+    for w in range(4):
+        res = rater.rate(roster, make_stream(spec, 5000, 3000, K=3, base=w * 5000), 3)
+    assert np.array_equal(got["status"], res.status.float().numpy())
+    for name, want in (("s_mu", res.s_mu), ("m_sig", res.m_sig), ("quality", res.quality),
+                       ("roster_mu", roster.state[:, 0::4]), ("roster_sigma", roster.state[:, 2::4])):
+        want = want.numpy()
+        assert np.array_equal(got[name + "_null"], np.isnan(want).astype(np.float32)), name
+        assert np.array_equal(got[name], np.nan_to_num(want, nan=0.0)), name
+    assert got["s_mu_null"].any() and got["roster_mu_null"].any() and not got["s_mu_null"].all()
+    # a larger output is sampled: sorted distinct rows, the same for the same seed
+    rows = bench._sample_rows(10 * bench.DUMP_ROWS, 7)
+    assert rows.numel() == bench.DUMP_ROWS and bool((rows[1:] > rows[:-1]).all()) and int(rows[-1]) < 10 * bench.DUMP_ROWS
+    assert torch.equal(rows, bench._sample_rows(10 * bench.DUMP_ROWS, 7))
+
+
+def _spawn_on_cpu(tmp_path, n, *extra):
     import json
     import subprocess
 
@@ -107,12 +174,29 @@ def test_multi_rank_json_contract_on_cpu(tmp_path, n):
         env.pop(var, None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--device", "cpu", "--gpus", str(n),
-                          "--players", "2000", "--matches-per-gpu", str(1000 * n), "--steps", "2", "--warmup", "1"],
-                         cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
+                          "--players", "2000", "--matches-per-gpu", str(1000 * n), "--steps", "2", "--warmup", "1"]
+                         + list(extra), cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout  # rank 0 only
-    j = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_plain_multi_rank_run_skips_the_accuracy_pass(tmp_path):
+    """Without --full an N > 1 run times its steps and prints the line: no accuracy block."""
+    j = _spawn_on_cpu(tmp_path, 2)
+    assert j["n_gpus"] == 2 and j["full"] is False and j["accuracy"] is None and j["merge_ms"]["buckets"] >= 1
+
+
+@pytest.mark.parametrize("n", [2, 4, 8])
+def test_multi_rank_json_contract_on_cpu(tmp_path, n):
+    """The N > 1 path of the driver contract end to end on the CPU (``--device cpu``:
+    host mirror, gloo): bench.py spawns its own N ranks (127.0.0.1 rendezvous), runs
+    one-prepass-per-step DP steps with a merge after each of k = N windows, and rank 0
+    prints ONE JSON line with the N > 1 keys -- the rank count, the merge split with the
+    prepass placement and, under --full, the accuracy block with the per-participant
+    record errors and the merge decodes' clamp count."""
+    j = _spawn_on_cpu(tmp_path, n, "--full")
     k = min(n, 8)
     assert j["n_gpus"] == n and j["rccl_world"] == n and j["dist_backend"] == "gloo" and j["device"] == "cpu"
     # the mode names the backend that merged (a gloo rehearsal never claims RCCL)

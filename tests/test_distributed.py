@@ -535,6 +535,10 @@ def _corrected_ring(rank, size, P, M, K, seed, windows, mode):
     assert merger.split() == (mode == "split"), (mode, merger.split())
     pipe = WindowPipeline(BatchRater(), roster, K, merger=merger)
     outs = [RateResult.allocate(M, K, "cpu") for _ in range(2)]
+    for o in outs:
+        # the rows are compared whole: a row's status is ONE byte of its last word, and
+        # allocate() leaves the word's other three bytes (row padding) unwritten
+        o.packed.zero_()
     prep = pipe.prepare(recs[0])
     for w in range(windows):
         _, prep = pipe.step(prep, recs[w + 1] if w + 1 < windows else None, out=outs[w % 2])
