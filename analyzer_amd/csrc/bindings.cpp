@@ -16,6 +16,7 @@
 #include "host.h"
 #include "ingest.h"
 #include "kernels.h"
+#include "select_core.h"
 
 namespace {
 
@@ -908,6 +909,52 @@ void records_digest(Tensor rows, int64_t K, Tensor scratch, Tensor out, const c1
 
 int64_t records_digest_scratch(int64_t K) { return (int64_t)ana::records_digest_scratch_doubles((int)K); }
 
+// K10 (select.hip; host mirror host.cpp records_select_host): hits [n, 12] int32 of the bitmap's
+// players in a window's records joined with its packed output rows, ascending (match, slot).
+// Dispatches on the tensors' device; the device path synchronises once to size hits exactly.
+Tensor records_select(Tensor rec, Tensor rows, int64_t base, int64_t P, Tensor bitmap) {
+  const auto dev = rec.device();
+  check(rec, "rec", torch::kInt32, dev);
+  check(rows, "rows", torch::kFloat32, dev);
+  check(bitmap, "bitmap", torch::kInt32, dev);
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) <= 12 && rec.size(1) % 2 == 0,
+              "records_select: rec must be [M, 2K+2] with K in 1..5");
+  const int64_t M = rec.size(0), K = (rec.size(1) - 2) / 2;
+  TORCH_CHECK(rows.dim() == 2 && rows.size(0) == M && rows.size(1) >= 10 * K + 2 && rows.size(1) % 4 == 0,
+              "records_select: rows must be the packed [M, W] output rows of rec's matches");
+  TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "records_select: P must fit in int32");
+  TORCH_CHECK(base >= 0, "records_select: base must be >= 0");
+  TORCH_CHECK(bitmap.dim() == 1 && bitmap.numel() >= (P + 31) / 32, "records_select: bitmap needs ceil(P / 32) words");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(rec.data_ptr()) % (K % 2 == 0 ? 8 : 16) == 0 &&
+                  reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0,
+              "records_select: rec and rows must be 16-B aligned");
+  const uint32_t* bm = reinterpret_cast<const uint32_t*>(bitmap.data_ptr<int32_t>());
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
+  if (!dev.is_cuda()) {
+    const int64_t n = ana::records_select_host((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1),
+                                               M, base, P, bm, nullptr);
+    Tensor hits = torch::empty({n, (int64_t)ana::kHitWords}, i32);
+    ana::records_select_host((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, base, P, bm,
+                             hits.data_ptr<int32_t>());
+    return hits;
+  }
+  const int64_t tiles = ana::records_select_tiles(M);
+  Tensor counts = torch::empty({tiles}, i32);
+  Tensor offsets = torch::empty({tiles + 1}, i32.dtype(torch::kInt64));
+  check_hip(ana::launch_records_select_count((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M,
+                                             P, bm, reinterpret_cast<uint32_t*>(counts.data_ptr<int32_t>()),
+                                             offsets.data_ptr<int64_t>(), stream_of(rec)),
+            "records_select (count)");
+  const int64_t n = offsets[tiles].item<int64_t>();  // the one synchronisation of a call
+  TORCH_CHECK(n >= 0 && n <= M * 2 * K, "records_select: impossible hit count ", n);
+  Tensor hits = torch::empty({n, (int64_t)ana::kHitWords}, i32);
+  check_hip(ana::launch_records_select_emit((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M,
+                                            base, P, bm, offsets.data_ptr<int64_t>(), hits.data_ptr<int32_t>(), n,
+                                            stream_of(rec)),
+            "records_select (emit)");
+  return hits;
+}
+
 void reset_tags(Tensor state) {
   const auto dev = state.device();
   check(state, "state", torch::kFloat32, dev);
@@ -983,6 +1030,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(+ its status counts added to hist)", py::arg("rows"), py::arg("K"), py::arg("scratch"),
         py::arg("out"), py::arg("hist") = py::none());
   m.def("records_digest_scratch", &records_digest_scratch, "scratch doubles of records_digest");
+  m.def("records_select", &records_select, "K10: hits [n, 12] int32 of the bitmap's players in a window's records "
+        "joined with its packed output rows, ascending (match, slot)", py::arg("rec"), py::arg("rows"),
+        py::arg("base"), py::arg("P"), py::arg("bitmap"));
+  m.attr("HIT_WORDS") = ana::kHitWords;
+  m.attr("SELECT_TILE") = ana::kSelectTile;
   m.def("emulate_allreduce", &emulate_allreduce,
         "DP pricing on one GPU: an all-reduce stand-in (buffer unchanged) on N CUs for >= us microseconds");
   m.def("warm_rows", &warm_rows, "read every roster row once (cache warm-up before a rating launch)");

@@ -12,6 +12,7 @@
 
 #include "gen_core.h"
 #include "rate_core.h"
+#include "select_core.h"
 
 namespace ana {
 
@@ -279,6 +280,41 @@ void host_prefix_delta(const float* s0, const float* prefix, const float* attrs,
                        float unknown_sigma, float* delta, int64_t P) {
   for (int64_t p = 0; p < P; ++p)
     prefix_delta_player(s0 + p * kBaseFloats, prefix + p * 14, attrs + p * 4, vst, unknown_sigma, delta + p * 16);
+}
+
+// K10: the device's three launches as one sequential walk (the order is the walk's)
+template <int K>
+static int64_t records_select_k(const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base, int64_t P,
+                                const uint32_t* bitmap, int32_t* hits) {
+  constexpr int S = 2 * K;
+  int64_t n = 0;
+  for (int64_t m = 0; m < M; ++m) {
+    const int32_t* r = rec + m * (S + 2);
+    const uint32_t mask = select_mask<K>(r, P, bitmap);
+    if (!mask) continue;  // the row is only read behind a bitmap hit
+    uint32_t row[5 * S + 2];
+    memcpy(row, rows + m * W, sizeof(row));
+    const uint32_t st = select_row_status<K>(row);
+    if (!select_status(st)) continue;
+    for (int j = 0; j < S; ++j) {
+      if (!((mask >> j) & 1u)) continue;
+      if (hits != nullptr) select_hit<K>(r, row, base + m, j, st, hits + n * kHitWords);
+      ++n;
+    }
+  }
+  return n;
+}
+
+int64_t records_select_host(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base,
+                            int64_t P, const uint32_t* bitmap, int32_t* hits) {
+  switch (K) {
+    case 1: return records_select_k<1>(rec, rows, W, M, base, P, bitmap, hits);
+    case 2: return records_select_k<2>(rec, rows, W, M, base, P, bitmap, hits);
+    case 3: return records_select_k<3>(rec, rows, W, M, base, P, bitmap, hits);
+    case 4: return records_select_k<4>(rec, rows, W, M, base, P, bitmap, hits);
+    case 5: return records_select_k<5>(rec, rows, W, M, base, P, bitmap, hits);
+    default: return -1;
+  }
 }
 
 }  // namespace ana

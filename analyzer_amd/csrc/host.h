@@ -40,4 +40,9 @@ void host_correct_records(int K, const int32_t* rec, int64_t M, float* rows, int
                           int64_t P);
 void host_prefix_delta(const float* s0, const float* prefix, const float* attrs, const float* vst,
                        float unknown_sigma, float* delta, int64_t P);
+// K10 host mirror (select_core.h): the hits of the bitmap's players in rec [M][2K+2] joined
+// with rows [M][W], ascending (match, slot), bit-identical to the device.  Returns their
+// number (-1: K out of range); hits == nullptr only counts.
+int64_t records_select_host(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base,
+                            int64_t P, const uint32_t* bitmap, int32_t* hits);
 }  // namespace ana

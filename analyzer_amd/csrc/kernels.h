@@ -36,6 +36,20 @@ size_t records_digest_scratch_doubles(int K);
 int launch_records_digest(int K, const float* rows, int64_t M, int64_t W, double* scratch, double* out,
                           int64_t* hist, hipStream_t s);
 
+// K10 records_select (select.hip, select_core.h): the hits [n][kHitWords] int32 of the players
+// of ``bitmap`` (uint32 [ceil(P / 32)]) in a window's records rec [M][2K+2] joined with its
+// packed output rows [M][W], in ascending (match, slot) order; base: global index of match 0.
+// rec and rows 16-B aligned (rec 8-B for K = 2, 4).  Two calls with one host read between them:
+// count fills counts [tiles] and offsets [tiles + 1] (exclusive scan; the total last), emit
+// writes hits [nhits] with nhits = offsets[tiles].
+constexpr int kSelectTile = 2048;  // matches per workgroup
+int64_t records_select_tiles(int64_t M);
+int launch_records_select_count(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P,
+                                const uint32_t* bitmap, uint32_t* counts, int64_t* offsets, hipStream_t s);
+int launch_records_select_emit(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base,
+                               int64_t P, const uint32_t* bitmap, const int64_t* offsets, int32_t* hits,
+                               int64_t nhits, hipStream_t s);
+
 // Stable LSD radix sort of (key, value) pairs on the low ``bits`` key bits
 // (radix_sort.hip).  Ping-pongs between the two buffer pairs; *result_in_alt
 // says which holds the result.  ws: radix_sort_workspace_bytes(n) bytes.

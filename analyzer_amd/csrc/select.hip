@@ -1,0 +1,244 @@
+// K10 records_select: the records of a set of players out of a window of the resident
+// record arena (runtime/records.py), in chronological order.
+//
+// The arena's rows hold no player ids -- those live in the match stream -- so a player's
+// history is a join of a window's records rec [M][2K+2] with its output rows [M][W]:
+// every occupied slot whose player is in the query bitmap and whose match has records
+// (select_core.h) becomes one 48-B hit.  Hits come out in ascending (match, slot) order
+// and the same bits on every run: no atomics, no communication between workgroups
+// inside a launch.  Three launches:
+//
+//   count  one workgroup per fixed tile of kSelectTile matches, one lane per match per
+//          iteration: the record is loaded with the widest vector loads its size allows
+//          (16 / 24 / 32 / 40 / 48 B for K = 1..5: 16-B loads, 8-B loads for K = 2, 4),
+//          the per-match hit mask popcounted and summed over the tile -> counts[tile]
+//   scan   one workgroup: exclusive scan of the tile counts -> offsets[tile], the total
+//          in offsets[tiles]
+//   emit   the same tile walk; a hit's index is offsets[tile] + the hits of the tile's
+//          earlier iterations + the waves before this one (LDS) + a shuffle scan over
+//          the lanes' counts; each hit is three 16-B stores.  A tile without hits ends
+//          at once, so a sparse query streams only rec (a quarter of the bytes of the
+//          rows): a row is read only after one of its match's ids hit the bitmap.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "common.h"
+#include "kernels.h"
+#include "select_core.h"
+
+namespace ana {
+
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v2i __attribute__((ext_vector_type(2)));
+
+constexpr int kSelectThreads = 256;
+constexpr int kSelectWaves = kSelectThreads / 64;
+constexpr int kSelectIters = kSelectTile / kSelectThreads;
+static_assert(kSelectTile % kSelectThreads == 0, "a tile is a whole number of iterations");
+
+// record m into registers: 16-B loads where the record size is a multiple of 16 B, else 8-B
+template <int K>
+__device__ __forceinline__ void load_record(const int32_t* __restrict__ rec, int64_t m, int32_t* r) {
+  constexpr int NW = 2 * K + 2;
+  const int32_t* p = rec + m * NW;
+  if constexpr (NW % 4 == 0) {
+#pragma unroll
+    for (int q = 0; q < NW / 4; ++q) {
+      const v4i x = reinterpret_cast<const v4i*>(p)[q];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) r[4 * q + c] = x[c];
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < NW / 2; ++q) {
+      const v2i x = reinterpret_cast<const v2i*>(p)[q];
+      r[2 * q] = x[0];
+      r[2 * q + 1] = x[1];
+    }
+  }
+}
+
+// the hit mask of match m (0 past the window's end) and its status byte; the row is
+// only touched when the mask is not empty
+template <int K>
+__device__ __forceinline__ uint32_t match_mask(const int32_t* __restrict__ rec, const uint32_t* __restrict__ rows,
+                                               int64_t W, int64_t M, int64_t m, int64_t P,
+                                               const uint32_t* __restrict__ bitmap, int32_t* r, uint32_t& st) {
+  st = 0u;
+  if (m >= M) return 0u;
+  load_record<K>(rec, m, r);
+  uint32_t mask = select_mask<K>(r, P, bitmap);
+  if (mask) {
+    st = select_row_status<K>(rows + m * W);
+    if (!select_status(st)) mask = 0u;
+  }
+  return mask;
+}
+
+template <int K>
+__global__ void __launch_bounds__(kSelectThreads) select_count_kernel(const int32_t* __restrict__ rec,
+                                                                      const uint32_t* __restrict__ rows, int64_t W,
+                                                                      int64_t M, int64_t P,
+                                                                      const uint32_t* __restrict__ bitmap,
+                                                                      uint32_t* __restrict__ counts) {
+  const int t = threadIdx.x;
+  const int64_t m0 = (int64_t)blockIdx.x * kSelectTile + t;
+  uint32_t n = 0u;
+#pragma unroll
+  for (int i = 0; i < kSelectIters; ++i) {
+    int32_t r[2 * K + 2];
+    uint32_t st;
+    n += (uint32_t)__popc(match_mask<K>(rec, rows, W, M, m0 + (int64_t)i * kSelectThreads, P, bitmap, r, st));
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o, 64);
+  __shared__ uint32_t wsum[kSelectWaves];
+  if ((t & 63) == 0) wsum[t >> 6] = n;
+  __syncthreads();
+  if (t == 0) {
+    uint32_t s = 0u;
+#pragma unroll
+    for (int w = 0; w < kSelectWaves; ++w) s += wsum[w];
+    counts[blockIdx.x] = s;
+  }
+}
+
+// one workgroup: lane l owns the tiles [l * per, (l + 1) * per)
+__global__ void __launch_bounds__(kSelectThreads) select_scan_kernel(const uint32_t* __restrict__ counts, int64_t tiles,
+                                                                     int64_t* __restrict__ offsets) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t per = (tiles + kSelectThreads - 1) / kSelectThreads;
+  const int64_t lo = (int64_t)t * per < tiles ? (int64_t)t * per : tiles;
+  const int64_t hi = lo + per < tiles ? lo + per : tiles;
+  int64_t own = 0;
+  for (int64_t i = lo; i < hi; ++i) own += counts[i];
+  int64_t incl = own;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int64_t v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  __shared__ int64_t wsum[kSelectWaves];
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  int64_t before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < kSelectWaves; ++w) {
+    before += w < wave ? wsum[w] : 0;
+    total += wsum[w];
+  }
+  int64_t run = before + incl - own;
+  for (int64_t i = lo; i < hi; ++i) {
+    offsets[i] = run;
+    run += counts[i];
+  }
+  if (t == 0) offsets[tiles] = total;
+}
+
+template <int K>
+__global__ void __launch_bounds__(kSelectThreads) select_emit_kernel(const int32_t* __restrict__ rec,
+                                                                     const uint32_t* __restrict__ rows, int64_t W,
+                                                                     int64_t M, int64_t base, int64_t P,
+                                                                     const uint32_t* __restrict__ bitmap,
+                                                                     const int64_t* __restrict__ offsets,
+                                                                     int32_t* __restrict__ hits, int64_t nhits) {
+  constexpr int S = 2 * K;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  int64_t run = offsets[blockIdx.x];
+  if (offsets[blockIdx.x + 1] == run) return;  // no hit in this tile (uniform over the workgroup)
+  const int64_t m0 = (int64_t)blockIdx.x * kSelectTile + t;
+  // per-wave sums, double-buffered over the iterations: one barrier per iteration
+  __shared__ int wsum[2][kSelectWaves];
+  for (int i = 0; i < kSelectIters; ++i) {
+    const int64_t m = m0 + (int64_t)i * kSelectThreads;
+    int32_t r[S + 2];
+    uint32_t st;
+    const uint32_t mask = match_mask<K>(rec, rows, W, M, m, P, bitmap, r, st);
+    const int own = __popc(mask);
+    int incl = own;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += v;
+    }
+    if (lane == 63) wsum[i & 1][wave] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kSelectWaves; ++w) {
+      const int s = wsum[i & 1][w];
+      before += w < wave ? s : 0;
+      total += s;
+    }
+    int64_t idx = run + before + incl - own;
+    run += total;
+    if (mask) {
+      const uint32_t* row = rows + m * W;
+#pragma unroll
+      for (int j = 0; j < S; ++j) {
+        if (!((mask >> j) & 1u)) continue;
+        if (idx < nhits) {  // always, for unchanged inputs: the counts come from the same walk
+          int32_t h[kHitWords];
+          select_hit<K>(r, row, base + m, j, st, h);
+          v4i* dst = reinterpret_cast<v4i*>(hits + idx * kHitWords);
+#pragma unroll
+          for (int q = 0; q < kHitWords / 4; ++q) {
+            v4i x;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) x[c] = h[4 * q + c];
+            dst[q] = x;
+          }
+        }
+        ++idx;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+int64_t records_select_tiles(int64_t M) { return (M + kSelectTile - 1) / kSelectTile; }
+
+int launch_records_select_count(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P,
+                                const uint32_t* bitmap, uint32_t* counts, int64_t* offsets, hipStream_t s) {
+  const int64_t tiles = records_select_tiles(M);
+  if (K < 1 || K > 5 || W < 5 * 2 * K + 2 || M < 0 || P < 0 || tiles > 0x7fffffffll) return (int)hipErrorInvalidValue;
+  const uint32_t* rw = reinterpret_cast<const uint32_t*>(rows);
+  if (tiles > 0) {
+    switch (K) {
+#define ANA_SELECT_CASE(k)                                                                                   \
+  case k:                                                                                                    \
+    hipLaunchKernelGGL(select_count_kernel<k>, dim3((unsigned)tiles), dim3(kSelectThreads), 0, s, rec, rw, W, M, P, \
+                       bitmap, counts);                                                                      \
+    break;
+      ANA_SELECT_CASE(1) ANA_SELECT_CASE(2) ANA_SELECT_CASE(3) ANA_SELECT_CASE(4) ANA_SELECT_CASE(5)
+#undef ANA_SELECT_CASE
+    }
+  }
+  hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(kSelectThreads), 0, s, counts, tiles, offsets);
+  return (int)hipGetLastError();
+}
+
+int launch_records_select_emit(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base,
+                               int64_t P, const uint32_t* bitmap, const int64_t* offsets, int32_t* hits,
+                               int64_t nhits, hipStream_t s) {
+  const int64_t tiles = records_select_tiles(M);
+  if (K < 1 || K > 5 || W < 5 * 2 * K + 2 || M < 0 || P < 0 || tiles > 0x7fffffffll) return (int)hipErrorInvalidValue;
+  if (tiles == 0 || nhits == 0) return 0;
+  const uint32_t* rw = reinterpret_cast<const uint32_t*>(rows);
+  switch (K) {
+#define ANA_SELECT_CASE(k)                                                                                  \
+  case k:                                                                                                   \
+    hipLaunchKernelGGL(select_emit_kernel<k>, dim3((unsigned)tiles), dim3(kSelectThreads), 0, s, rec, rw, W, M, base, \
+                       P, bitmap, offsets, hits, nhits);                                                    \
+    break;
+    ANA_SELECT_CASE(1) ANA_SELECT_CASE(2) ANA_SELECT_CASE(3) ANA_SELECT_CASE(4) ANA_SELECT_CASE(5)
+#undef ANA_SELECT_CASE
+  }
+  return (int)hipGetLastError();
+}
+
+}  // namespace ana

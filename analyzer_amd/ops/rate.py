@@ -152,7 +152,17 @@ class RateResult:
             return RateResult(torch.empty(M, **f), torch.empty(M, dtype=torch.uint8, device=device),
                               *(torch.empty((M, S), **f) for _ in range(5)))
         W = RateResult.row_floats(K)
-        buf = torch.empty((M, W), dtype=torch.float32, device=device)
+        return RateResult.from_packed(torch.empty((M, W), dtype=torch.float32, device=device), K)
+
+    @staticmethod
+    def from_packed(buf: torch.Tensor, K: int) -> "RateResult":
+        """The field views of packed rows ``buf`` [M, row_floats(K)] (no copy): what
+        ``allocate`` builds, over memory the caller owns (a slice of the record arena,
+        runtime/records.py)."""
+        S = 2 * K
+        if buf.dim() != 2 or buf.shape[1] != RateResult.row_floats(K) or buf.dtype != torch.float32 \
+                or not buf.is_contiguous():
+            raise ValueError("packed rows must be a contiguous fp32 [M, %d]" % RateResult.row_floats(K))
         slots = [buf[:, f * S:(f + 1) * S] for f in range(5)]
         status = buf.view(torch.uint8)[:, 4 * (5 * S + 1)]
         return RateResult(buf[:, 5 * S], status, *slots, packed=buf)

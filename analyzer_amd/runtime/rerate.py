@@ -23,12 +23,21 @@ streams a long synthetic history through the engine window by window:
   digests of the windows it re-rates); ``records="host"`` streams them D2H into
   a ring of pinned buffers on a copy stream, overlapped with the next windows
   (double-buffered device outputs), and hands them to ``on_records``;
+  ``records="resident"`` keeps them on the device: every window is rated straight
+  into its slice of a ``RecordArena`` (runtime/records.py; 128 B per 3v3 match, so
+  1B matches are 128 GB on one GPU, 16 GB per GPU on 8), still digested per window,
+  and ``arena.history`` selects the records of a set of players out of it in
+  chronological order (csrc/select.hip).  Checkpoints do not hold arena rows: a
+  resumed run fills a fresh arena from the resume point on (``arena.first_match``),
+  and ``arena.export`` / ``RecordArena.load`` persist one;
 * status counters are accumulated on the device and reduced over ranks (C4);
   the executor's error flags are sticky over windows and checked before every
   checkpoint, so a failed middle window is never checkpointed over.
 
     python -m analyzer_amd.runtime.rerate --matches 1000000000 --players 10000000 \\
         --window 16000000 --team-size 3 --checkpoint-dir /tmp/ck
+    python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
+        --window 16000000 --records resident --history 17,4242 --export-records /data/records.bin
 """
 from __future__ import annotations
 
@@ -52,6 +61,7 @@ from ..utils.trace import trace_range
 from .checkpoint import CheckpointManager
 from .engine import WindowPipeline
 from .ingest import OutputSink
+from .records import RecordArena, local_extent
 
 
 class InjectedFault(SystemExit):
@@ -147,14 +157,28 @@ def run(spec: RerateSpec, device=None, checkpoint_dir: Optional[str] = None,
         on_window: Optional[Callable[[int, R.RateResult], None]] = None,
         rater: Optional[R.BatchRater] = None, comm_dtype: Optional[str] = None,
         records: str = "digest", on_records: Optional[Callable[[int, dict], None]] = None,
-        sweeps: int = 1):
+        sweeps: int = 1, arena: Optional[RecordArena] = None):
     """Rate the whole history; returns (metrics reduced over ranks, final roster).
 
     ``records``: "digest" (device reduction per window, in the metrics as
     ``window_digests``), "host" (pinned D2H ring; ``on_records(base, host_dict)``
-    gets every window's rows) or "none"."""
-    if records not in ("digest", "host", "none"):
-        raise ValueError("records must be digest, host or none")
+    gets every window's rows), "none", or "resident": every window is rated straight
+    into its slice of ``arena`` (runtime/records.py; required in this mode --
+    ``rerate_resident`` plans and allocates one) and the digests are computed from
+    the arena slices, so ``window_digests`` stay comparable across modes.
+
+    Arena rows are not written into checkpoints (the meta only names the mode and the
+    arena's filled extent): a resumed resident run needs a fresh arena whose
+    ``first_match`` is the resume offset; it holds the windows from the resume point
+    on, and ``arena.history`` over it returns only those.  ``arena.export`` persists
+    an arena."""
+    if records not in ("digest", "host", "none", "resident"):
+        raise ValueError("records must be digest, host, none or resident")
+    resident = records == "resident"
+    if resident and arena is None:
+        raise ValueError("records='resident' needs an arena (rerate_resident plans and allocates one)")
+    if arena is not None and not resident:
+        raise ValueError("an arena is only filled with records='resident'")
     rank, size = world()
     dev = torch.device(device) if device is not None else (
         torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu"))
@@ -173,6 +197,14 @@ def run(spec: RerateSpec, device=None, checkpoint_dir: Optional[str] = None,
     else:
         roster = make_roster(spec.roster_spec(), device=dev)
         broadcast_roster(roster)  # C3 (identical by construction; keeps replicas honest)
+    if resident:
+        first = window_slice(spec, start_window, 0, size)[0]
+        if (arena.K, arena.rank, arena.size, arena.window, arena.first_match) != (K, rank, size, spec.window, first) \
+                or arena.matches < local_extent(spec.total_matches, spec.window, rank, size, first) \
+                or arena.filled or arena.device.type != dev.type:
+            raise ValueError("the arena does not match this run: it must be empty, on %s, of team size %d, rank %d "
+                             "of %d, window %d, and hold the matches from %d on"
+                             % (dev.type, K, rank, size, spec.window, first))
     comm_dtype = comm_dtype or default_comm_dtype(sweeps)
     merger = (SweepMerger(spec.players, dev, rater.cfg, comm_dtype=comm_dtype, sweeps=sweeps)
               if size > 1 else None)
@@ -216,15 +248,19 @@ def run(spec: RerateSpec, device=None, checkpoint_dir: Optional[str] = None,
         cur = ahead.popleft()
         M = cur.rec.shape[0]
         b = g & 1
-        if outs[b] is None or outs[b].quality.shape[0] != M:
-            outs[b] = R.RateResult.allocate(M, K, dev)
-        elif sink is not None and sink.copied(outs[b]) is not None:
-            torch.cuda.current_stream(dev).wait_event(sink.copied(outs[b]))
+        if resident:  # rated in place: the window's slice of the arena, no double buffer
+            out = arena.result(*window_slice(spec, g, rank, size), fill=True)
+        else:
+            if outs[b] is None or outs[b].quality.shape[0] != M:
+                outs[b] = R.RateResult.allocate(M, K, dev)
+            elif sink is not None and sink.copied(outs[b]) is not None:
+                torch.cuda.current_stream(dev).wait_event(sink.copied(outs[b]))
+            out = outs[b]
         nw = g + D  # the window prepared behind this rating
         if gen_tail and nw < total:
             # window g+D is generated on the prepass stream in rate(g)'s tail, right before
             # its prepass, instead of on the main stream in front of rate(g)
-            res = pipe.rate(cur, out=outs[b])
+            res = pipe.rate(cur, out=out)
             side = pipe.side
             with torch.cuda.stream(side):
                 pipe.wait_tail(side)
@@ -235,11 +271,13 @@ def run(spec: RerateSpec, device=None, checkpoint_dir: Optional[str] = None,
             ahead.append(pipe.prepare(rec_next, produced=made))
         else:
             # window g+D is generated before rate(g) is enqueued; its prepass waits for the tail
-            res, nxt = pipe.step(cur, window_rec(nw) if nw < total else None, out=outs[b])
+            res, nxt = pipe.step(cur, window_rec(nw) if nw < total else None, out=out)
             if nxt is not None:
                 ahead.append(nxt)
         pipe.results_ready(res)  # the DP merge's deferred record correction of these rows
-        if records == "digest":
+        if resident:
+            arena.commit()  # the slice is final (stream-ordered)
+        if records == "digest" or resident:
             digests[g] = digest(res, K, counts)  # + the status counts
         else:
             counts += torch.bincount(res.status.to(torch.int64), minlength=256)
@@ -256,7 +294,10 @@ def run(spec: RerateSpec, device=None, checkpoint_dir: Optional[str] = None,
             if rank == 0:
                 with trace_range("checkpoint", window=g + 1):
                     ck.maybe_save(g + 1, roster, {"spec": asdict(spec), "world": size,
-                                                  "next_offset": window_slice(spec, g + 1, 0, size)[0]})
+                                                  "next_offset": window_slice(spec, g + 1, 0, size)[0],
+                                                  # the arena's rows are not saved, only how far it was filled
+                                                  "records": records,
+                                                  "arena_extent": arena.filled if resident else None})
         if fault_kill_after is not None and g + 1 >= fault_kill_after:
             # the simulated crash hits once the checkpoints submitted so far are
             # committed (asynchronous writes, runtime/checkpoint.py): a real crash
@@ -278,7 +319,7 @@ def run(spec: RerateSpec, device=None, checkpoint_dir: Optional[str] = None,
     c = counts.cpu()
     local = {R.STATUS_NAMES.get(i, str(i)): float(c[i]) for i in range(256) if int(c[i])}
     local["matches"] = float(rated)
-    if records == "digest" and digests:
+    if (records == "digest" or resident) and digests:
         d = torch.stack([digests[g] for g in sorted(digests)]).cpu()
         local["match_records"] = float(d[:, 0].sum())
         local["participant_records"] = float(d[:, 1].sum())
@@ -292,9 +333,76 @@ def run(spec: RerateSpec, device=None, checkpoint_dir: Optional[str] = None,
     summed["matches_per_s"] = summed["matches"] / summed["seconds"] if summed["seconds"] > 0 else 0.0
     if rank == 0:
         summed.update({"checkpoint_" + k: v for k, v in ck.stats().items()})
-    if records == "digest":
+    if records == "digest" or resident:
         summed["window_digests"] = {g: digests[g].cpu().tolist() for g in sorted(digests)}
     return summed, roster
+
+
+class ArenaDoesNotFit(MemoryError):
+    """``rerate_resident``: the planned arena would not leave the reserve free
+    (``plan``: the ``RecordArena.plan`` report)."""
+
+    def __init__(self, plan: dict):
+        super().__init__("a resident record arena of %d bytes per rank (+ %d roster bytes) does not fit %d free "
+                         "bytes with %d in reserve" % (plan["arena_bytes_per_rank"], plan["roster_bytes"],
+                                                       plan["free_bytes"], plan["reserve_bytes"]))
+        self.plan = plan
+
+
+def resume_offset(spec: RerateSpec, checkpoint_dir: Optional[str], size: int) -> int:
+    """Global match offset a run over ``checkpoint_dir`` starts from (0 without a checkpoint)."""
+    ck = CheckpointManager(checkpoint_dir)
+    if not ck.path:
+        return 0
+    for cand in (ck.path, ck.path + ".old"):  # CheckpointManager.latest's order
+        meta, tensors = os.path.join(cand, "meta.json"), os.path.join(cand, "roster.safetensors")
+        if os.path.exists(meta) and os.path.exists(tensors):
+            with open(meta) as f:
+                return window_slice(spec, int(json.load(f)["windows_done"]), 0, size)[0]
+    return 0
+
+
+def stream_records(spec: RerateSpec, device) -> Callable[[int, int], torch.Tensor]:
+    """``rec_of`` for ``RecordArena.history``: the records of global matches [lo, hi),
+    regenerated from the run's counter-RNG stream."""
+    sspec = spec.stream_spec()
+    return lambda lo, hi: make_stream(sspec, hi - lo, spec.players, K=spec.team_size, base=lo, device=device)
+
+
+def rerate_resident(spec: RerateSpec, device=None, checkpoint_dir: Optional[str] = None,
+                    free_bytes: Optional[int] = None, plan: Optional[dict] = None, **kwargs):
+    """``run(..., records="resident")`` with an arena of its own: plans it
+    (``RecordArena.plan``; ``ArenaDoesNotFit`` when it would not leave the reserve),
+    allocates it for this rank from the checkpoint's resume point on and runs.
+    Returns (metrics, roster, arena); the metrics carry the plan as ``arena_plan``."""
+    rank, size = world()
+    dev = torch.device(device) if device is not None else (
+        torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu"))
+    if plan is None:
+        plan = RecordArena.plan(spec.total_matches, spec.team_size, dev, size=size, roster_players=spec.players,
+                                free_bytes=free_bytes, window=spec.window)
+    if not plan["fits"]:
+        raise ArenaDoesNotFit(plan)
+    first = resume_offset(spec, checkpoint_dir, size)
+    arena = RecordArena(local_extent(spec.total_matches, spec.window, rank, size, first), spec.team_size, dev,
+                        first_match=first, rank=rank, size=size, window=spec.window)
+    metrics, roster = run(spec, dev, checkpoint_dir=checkpoint_dir, records="resident", arena=arena, **kwargs)
+    metrics["arena_plan"] = plan
+    return metrics, roster, arena
+
+
+def _timeline(hist: dict, player: int) -> dict:
+    """One player's rows of a ``RecordArena.history`` result as JSON-ready lists (NaN -> null)."""
+    sel = (hist["player"] == player).nonzero().reshape(-1)
+    line = {"player": int(player), "records": int(sel.numel())}
+    for name, col in hist.items():
+        if name == "player":
+            continue
+        vals = col.index_select(0, sel).cpu().tolist()
+        if col.dtype.is_floating_point:
+            vals = [None if v != v else v for v in vals]
+        line[name] = vals
+    return line
 
 
 def main(argv=None) -> int:
@@ -312,18 +420,47 @@ def main(argv=None) -> int:
     ap.add_argument("--device", default=None)
     ap.add_argument("--comm-dtype", default=ecfg.comm_dtype or None,
                     choices=["fp32", "fp16", "bf16"], help="sweep-merge message precision")
-    ap.add_argument("--records", default="digest", choices=["digest", "host", "none"],
-                    help="output records: device digest per window, pinned D2H stream, or dropped")
+    ap.add_argument("--records", default="digest", choices=["digest", "host", "none", "resident"],
+                    help="output records: device digest per window, pinned D2H stream, dropped, or kept in a "
+                         "device-resident arena (prints the arena's sizing plan first; exit code 2 if it does not fit)")
+    ap.add_argument("--history", default=None, metavar="ID[,ID...]",
+                    help="with --records resident: print each player's timeline after the run (JSON lines)")
+    ap.add_argument("--export-records", default=None, metavar="PATH",
+                    help="with --records resident: write the arena to PATH (+ PATH.json; .rN appended on N ranks)")
+    ap.add_argument("--arena-free-bytes", type=float, default=None,
+                    help="plan the arena against this many free bytes instead of the device's")
     ap.add_argument("--sweeps", type=int, default=ecfg.sweeps, help="causal sweeps per window (N ranks)")
     ap.add_argument("--digests", action="store_true", help="print every window's digest")
     args = ap.parse_args(argv)
     rank, size, dev = init_from_env()
     spec = RerateSpec(total_matches=int(args.matches), players=int(args.players),
                       team_size=args.team_size, window=int(args.window), seed=args.seed)
+    resident = args.records == "resident"
+    if (args.history or args.export_records) and not resident:
+        ap.error("--history and --export-records need --records resident")
+    arena = None
     try:
-        res, roster = run(spec, args.device or dev, args.checkpoint_dir, args.checkpoint_every,
-                          args.fault_kill_after, comm_dtype=args.comm_dtype, records=args.records,
-                          sweeps=args.sweeps)
+        if resident:
+            plan = RecordArena.plan(spec.total_matches, spec.team_size, args.device or dev, size=size,
+                                    roster_players=spec.players, window=spec.window,
+                                    free_bytes=None if args.arena_free_bytes is None else int(args.arena_free_bytes))
+            if rank == 0:
+                print(json.dumps({"arena_plan": plan}), flush=True)
+            if not plan["fits"]:
+                print("the record arena does not fit: %d bytes per rank + %d roster bytes would leave %d of %d free "
+                      "bytes, less than the reserve of %d; use fewer matches, more ranks or another --records mode"
+                      % (plan["arena_bytes_per_rank"], plan["roster_bytes"], plan["left_bytes"], plan["free_bytes"],
+                         plan["reserve_bytes"]), file=sys.stderr, flush=True)
+                return 2
+            res, roster, arena = rerate_resident(spec, args.device or dev, args.checkpoint_dir, plan=plan,
+                                                 checkpoint_every=args.checkpoint_every,
+                                                 fault_kill_after=args.fault_kill_after, comm_dtype=args.comm_dtype,
+                                                 sweeps=args.sweeps)
+            res.pop("arena_plan", None)  # printed above
+        else:
+            res, roster = run(spec, args.device or dev, args.checkpoint_dir, args.checkpoint_every,
+                              args.fault_kill_after, comm_dtype=args.comm_dtype, records=args.records,
+                              sweeps=args.sweeps)
     except InjectedFault:
         if rank == 0:
             print(json.dumps({"fault_injected_after_windows": args.fault_kill_after}), flush=True)
@@ -338,7 +475,17 @@ def main(argv=None) -> int:
 
         res["roster_sha256"] = hashlib.sha256(
             roster.state[:, 0::2].contiguous().cpu().numpy().tobytes()).hexdigest()
+        if arena is not None:
+            res["arena_rows"], res["arena_first_match"] = arena.filled, arena.first_match
         print(json.dumps(dict(res, n_ranks=size, spec=asdict(spec))), flush=True)
+    if args.history:
+        ids = [int(p) for p in args.history.split(",") if p.strip()]
+        hist = arena.history(ids, spec.players, stream_records(spec, arena.device))  # this rank's hits
+        for p in ids:
+            print(json.dumps(dict(_timeline(hist, p), rank=rank)), flush=True)
+    if args.export_records:
+        path = args.export_records + (".r%d" % rank if size > 1 else "")
+        print(json.dumps({"exported": path, "bytes": arena.export(path), "rank": rank}), flush=True)
     return 0
 
 
