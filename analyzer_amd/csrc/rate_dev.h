@@ -11,8 +11,10 @@
 //    a = v rsq(c2), w / c2 = w rsq(c2)^2 -- no sqrt, no division;
 //  * v/w without erfc: a branch-free rational form of the Mills ratio (below), one
 //    formula for wins, losses and big upsets, evaluated for both tracks at once.
-// The host mirror (host.cpp -> rate_core.h, fp64) stays the oracle; this form agrees
-// with it within the device tolerances of tests/test_engine_gpu.py.
+// The host mirror (host.cpp -> rate_core.h, fp64) stays the oracle of whole windows
+// (tests/test_engine_gpu.py).  One match is held to a per-element error budget against
+// 50-digit mpmath, derived from the v/w bounds below and the fp32 roundings of this
+// chain: docs/ARCHITECTURE.md "Single-match error budget", tests/test_single_match.py.
 #pragma once
 
 #include <hip/hip_runtime.h>
