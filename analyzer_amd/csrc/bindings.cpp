@@ -16,6 +16,7 @@
 #include "host.h"
 #include "ingest.h"
 #include "kernels.h"
+#include "ladder_core.h"
 #include "select_core.h"
 
 namespace {
@@ -955,6 +956,79 @@ Tensor records_select(Tensor rec, Tensor rows, int64_t base, int64_t P, Tensor b
   return hits;
 }
 
+// K11 (ladder.hip; host mirror host.cpp host_ladder): the ladders of the tracks of ``mask``
+// (bit t = granule t) of a roster's state [P, 32], as [order, score, rank] per track in
+// ascending track order: order int32 [R] (best first), score fp32 [R], rank int32 [P]
+// (-1 = unranked).  Dispatches on the tensor's device; the device path reads the roster
+// once for all tracks and synchronises once, for the ranked counts that size the outputs.
+std::vector<Tensor> ladder(Tensor state, int64_t mask, int64_t score, double max_sigma) {
+  const auto dev = state.device();
+  check(state, "state", torch::kFloat32, dev);
+  TORCH_CHECK(state.dim() == 2 && state.size(1) == ana::kRowFloats, "ladder: state must be [P, 32]");
+  TORCH_CHECK(mask > 0 && (mask & ~(int64_t)ana::kLadderTrackMask) == 0,
+              "ladder: the track mask must name some of tracks 0..6");
+  TORCH_CHECK(score == ana::kLadderConservative || score == ana::kLadderMu, "ladder: unknown score ", score);
+  const int64_t P = state.size(0);
+  TORCH_CHECK(P <= 0x7fffffffLL, "ladder: P must be below 2^31");
+  const float bound = (float)max_sigma;
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
+  const auto f32 = i32.dtype(torch::kFloat32);
+  std::vector<int> tracks;
+  for (int t = 0; t < ana::kTracks; ++t)
+    if ((mask >> t) & 1) tracks.push_back(t);
+  const int64_t T = (int64_t)tracks.size();
+  std::vector<Tensor> out;
+  if (P == 0) {
+    for (int64_t j = 0; j < T; ++j) {
+      out.push_back(torch::empty({0}, i32));
+      out.push_back(torch::empty({0}, f32));
+      out.push_back(torch::empty({0}, i32));
+    }
+    return out;
+  }
+  if (!dev.is_cuda()) {
+    for (int64_t j = 0; j < T; ++j) {
+      Tensor order = torch::empty({P}, i32), sc = torch::empty({P}, f32), rank = torch::empty({P}, i32);
+      const int64_t R = ana::host_ladder(state.data_ptr<float>(), P, tracks[j], (int)score, bound,
+                                         order.data_ptr<int32_t>(), sc.data_ptr<float>(), rank.data_ptr<int32_t>());
+      TORCH_CHECK(R >= 0 && R <= P, "ladder: bad arguments");
+      out.push_back(R == P ? order : order.narrow(0, 0, R).clone());
+      out.push_back(R == P ? sc : sc.narrow(0, 0, R).clone());
+      out.push_back(rank);
+    }
+    return out;
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(state.data_ptr()) % 16 == 0, "ladder: state must be 16-B aligned");
+  const hipStream_t s = stream_of(state);
+  const int64_t stride = (P + 31) / 32 * 32;  // every track's keys start on a 128-B line
+  Tensor keys = torch::empty({T, stride}, i32), ids = torch::empty({T, stride}, i32);
+  Tensor counts = torch::empty({(int64_t)ana::kTracks}, i32);
+  auto u = [](Tensor& t) { return reinterpret_cast<uint32_t*>(t.data_ptr<int32_t>()); };
+  check_hip(ana::launch_ladder_keys(state.data_ptr<float>(), P, (uint32_t)mask, (int)score, bound, u(keys), u(ids),
+                                    stride, u(counts), s),
+            "ladder_keys");
+  const Tensor host_counts = counts.cpu();  // the one synchronisation of a build
+  // the sort's work buffers, shared by the tracks
+  Tensor kalt = torch::empty({P}, i32), valt = torch::empty({P}, i32);
+  Tensor ws = torch::empty({(int64_t)ana::radix_sort_workspace_bytes(P)}, i32.dtype(torch::kUInt8));
+  for (int64_t j = 0; j < T; ++j) {
+    const int64_t R = host_counts.data_ptr<int32_t>()[j];
+    TORCH_CHECK(R >= 0 && R <= P, "ladder: impossible ranked count ", R);
+    uint32_t *k = u(keys) + j * stride, *v = u(ids) + j * stride;
+    int in_alt = 0;
+    check_hip(ana::launch_radix_sort_pairs(k, v, u(kalt), u(valt), P, 32, ws.data_ptr<uint8_t>(), &in_alt, s),
+              "ladder (sort)");
+    Tensor order = torch::empty({R}, i32), sc = torch::empty({R}, f32), rank = torch::empty({P}, i32);
+    check_hip(ana::launch_ladder_ranks(in_alt ? u(kalt) : k, in_alt ? u(valt) : v, P, R, order.data_ptr<int32_t>(),
+                                       sc.data_ptr<float>(), rank.data_ptr<int32_t>(), s),
+              "ladder_ranks");
+    out.push_back(order);
+    out.push_back(sc);
+    out.push_back(rank);
+  }
+  return out;
+}
+
 void reset_tags(Tensor state) {
   const auto dev = state.device();
   check(state, "state", torch::kFloat32, dev);
@@ -1033,6 +1107,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("records_select", &records_select, "K10: hits [n, 12] int32 of the bitmap's players in a window's records "
         "joined with its packed output rows, ascending (match, slot)", py::arg("rec"), py::arg("rows"),
         py::arg("base"), py::arg("P"), py::arg("bitmap"));
+  m.def("ladder", &ladder, "K11: [order, score, rank] per track of the mask (bit t = granule t) of a roster's state: "
+        "descending score, ties by ascending id, rank -1 = unranked", py::arg("state"), py::arg("mask"),
+        py::arg("score"), py::arg("max_sigma"));
+  m.attr("LADDER_CONSERVATIVE") = (int)ana::kLadderConservative;
+  m.attr("LADDER_MU") = (int)ana::kLadderMu;
   m.attr("HIT_WORDS") = ana::kHitWords;
   m.attr("SELECT_TILE") = ana::kSelectTile;
   m.def("emulate_allreduce", &emulate_allreduce,

@@ -8,9 +8,11 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "gen_core.h"
+#include "ladder_core.h"
 #include "rate_core.h"
 #include "select_core.h"
 
@@ -315,6 +317,34 @@ int64_t records_select_host(int K, const int32_t* rec, const float* rows, int64_
     case 5: return records_select_k<5>(rec, rows, W, M, base, P, bitmap, hits);
     default: return -1;
   }
+}
+
+// K11: the device's three stages on one track -- keys in id order, a stable sort of the
+// ids by key, ranks from the sorted positions (ladder_core.h)
+int64_t host_ladder(const float* state, int64_t P, int track, int score, float max_sigma, int32_t* order,
+                    float* score_out, int32_t* rank) {
+  if (track < 0 || track >= kTracks || P < 0 || P > 0x7fffffffll ||
+      (score != kLadderConservative && score != kLadderMu))
+    return -1;
+  std::vector<uint32_t> keys((size_t)P);
+  std::vector<int32_t> ids((size_t)P);
+  int64_t R = 0;
+  for (int64_t p = 0; p < P; ++p) {
+    const float* g = state + p * kRowFloats + 4 * track;
+    keys[p] = ladder_key(g[0], g[2], score, max_sigma);
+    ids[p] = (int32_t)p;
+    R += keys[p] != kLadderUnranked;
+  }
+  std::stable_sort(ids.begin(), ids.end(), [&](int32_t a, int32_t b) { return keys[a] < keys[b]; });
+  for (int64_t i = 0; i < P; ++i) {
+    const int32_t id = ids[i];
+    rank[id] = i < R ? (int32_t)i : -1;
+    if (i < R) {
+      order[i] = id;
+      score_out[i] = ladder_key_score(keys[id]);
+    }
+  }
+  return R;
 }
 
 }  // namespace ana

@@ -45,4 +45,9 @@ void host_prefix_delta(const float* s0, const float* prefix, const float* attrs,
 // number (-1: K out of range); hits == nullptr only counts.
 int64_t records_select_host(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base,
                             int64_t P, const uint32_t* bitmap, int32_t* hits);
+// K11 host mirror (ladder_core.h): the ladder of one track (granule 0..6) of state [P][32]:
+// order / score_out (the first R of [P] entries are written) and rank [P] (-1: unranked),
+// bit-identical to the device.  Returns R, the number of ranked players (-1: bad arguments).
+int64_t host_ladder(const float* state, int64_t P, int track, int score, float max_sigma, int32_t* order,
+                    float* score_out, int32_t* rank);
 }  // namespace ana

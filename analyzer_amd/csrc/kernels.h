@@ -50,6 +50,19 @@ int launch_records_select_emit(int K, const int32_t* rec, const float* rows, int
                                int64_t P, const uint32_t* bitmap, const int64_t* offsets, int32_t* hits,
                                int64_t nhits, hipStream_t s);
 
+// K11 ladder (ladder.hip, ladder_core.h).  ladder_keys: one pass over state [P][32] for the
+// tracks of ``mask`` (bit t = granule t, 0..6); track slot j (the j-th set bit) gets its
+// sort keys in keys[j * stride ..) and the identity permutation in ids[j * stride ..)
+// (stride >= P, a multiple of 4 words; state, keys, ids 16-B aligned), and counts[j] its
+// number of ranked players (counts: kTracks words, zeroed by the launch).  The pairs are
+// sorted with launch_radix_sort_pairs (32 bits); ladder_ranks then turns one track's sorted
+// (keys, ids) [P] and its count R into order [R], score [R] and rank [P].
+constexpr int kLadderTile = 1024;  // players per workgroup
+int launch_ladder_keys(const float* state, int64_t P, uint32_t mask, int score, float max_sigma, uint32_t* keys,
+                       uint32_t* ids, int64_t stride, uint32_t* counts, hipStream_t s);
+int launch_ladder_ranks(const uint32_t* keys, const uint32_t* ids, int64_t P, int64_t R, int32_t* order, float* score,
+                        int32_t* rank, hipStream_t s);
+
 // Stable LSD radix sort of (key, value) pairs on the low ``bits`` key bits
 // (radix_sort.hip).  Ping-pongs between the two buffer pairs; *result_in_alt
 // says which holds the result.  ws: radix_sort_workspace_bytes(n) bytes.

@@ -1,2 +1,3 @@
 """Batched tensor operators of the rating engine (HIP kernels on MI355X)."""
 from .native import native, is_built  # noqa: F401
+from .ladder import Ladder, build_ladder  # noqa: F401

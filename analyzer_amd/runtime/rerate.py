@@ -38,6 +38,8 @@ streams a long synthetic history through the engine window by window:
         --window 16000000 --team-size 3 --checkpoint-dir /tmp/ck
     python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
         --window 16000000 --records resident --history 17,4242 --export-records /data/records.bin
+    python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
+        --window 16000000 --ladder shared,ranked --ladder-top 10 --ladder-rank 17,4242
 """
 from __future__ import annotations
 
@@ -54,6 +56,7 @@ import torch
 
 from ..config import EngineConfig, RaterConfig
 from ..ops import rate as R
+from ..ops.ladder import build_ladder, track_index
 from ..ops.synth import RosterSpec, StreamSpec, make_roster, make_stream
 from ..parallel.comm import broadcast_roster, init_from_env, reduce_counts, world
 from ..parallel.sweep import SweepMerger
@@ -405,6 +408,29 @@ def _timeline(hist: dict, player: int) -> dict:
     return line
 
 
+def _num(v: float):
+    return None if v != v else v  # NaN -> null
+
+
+def ladder_lines(roster: R.Roster, tracks, top: int = 10, ids=(), score: str = "conservative") -> list:
+    """One JSON-ready dict per track of ``tracks`` from ``roster`` (ops/ladder.py, one build for
+    all tracks): the ladder's size, its best ``top`` players and the standing of ``ids``."""
+    lad = build_ladder(roster, tracks, score=score)
+    lines = []
+    for name in tracks:
+        t_ids, t_mu, t_sig, t_score = (x.cpu().tolist() for x in lad.top(name, top))
+        line = {"ladder": name, "score": score, "players": lad.num_players, "ranked": lad.ranked(name),
+                "top": [{"rank": i, "player": p, "mu": _num(m), "sigma": _num(sg), "score": _num(sc)}
+                        for i, (p, m, sg, sc) in enumerate(zip(t_ids, t_mu, t_sig, t_score))],
+                "ranks": []}
+        if len(ids):
+            rank, sc, pct = (x.cpu().tolist() for x in lad.lookup(name, list(ids)))
+            line["ranks"] = [{"player": int(p), "rank": r, "score": _num(s_), "percentile": _num(q)}
+                             for p, r, s_, q in zip(ids, rank, sc, pct)]
+        lines.append(line)
+    return lines
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--matches", type=float, required=True)
@@ -429,6 +455,12 @@ def main(argv=None) -> int:
                     help="with --records resident: write the arena to PATH (+ PATH.json; .rN appended on N ranks)")
     ap.add_argument("--arena-free-bytes", type=float, default=None,
                     help="plan the arena against this many free bytes instead of the device's")
+    ap.add_argument("--ladder", default=None, metavar="TRACK[,TRACK...]",
+                    help="print the final roster's ladder of each track after the run (JSON lines): shared or a "
+                         "mode, ranked by conservative skill mu - sigma, ties by player id")
+    ap.add_argument("--ladder-top", type=int, default=10, metavar="K", help="with --ladder: the best K players")
+    ap.add_argument("--ladder-rank", default=None, metavar="ID[,ID...]",
+                    help="with --ladder: also the rank, score and percentile of these players")
     ap.add_argument("--sweeps", type=int, default=ecfg.sweeps, help="causal sweeps per window (N ranks)")
     ap.add_argument("--digests", action="store_true", help="print every window's digest")
     args = ap.parse_args(argv)
@@ -438,6 +470,17 @@ def main(argv=None) -> int:
     resident = args.records == "resident"
     if (args.history or args.export_records) and not resident:
         ap.error("--history and --export-records need --records resident")
+    if args.ladder_rank and not args.ladder:
+        ap.error("--ladder-rank needs --ladder")
+    ladder_tracks = [t.strip() for t in (args.ladder or "").split(",") if t.strip()]
+    ladder_ids = [int(p) for p in (args.ladder_rank or "").split(",") if p.strip()]
+    try:
+        for t in ladder_tracks:
+            track_index(t)
+    except ValueError as e:
+        ap.error(str(e))
+    if any(p < 0 or p >= spec.players for p in ladder_ids):
+        ap.error("--ladder-rank ids must lie in [0, %d)" % spec.players)
     arena = None
     try:
         if resident:
@@ -483,6 +526,9 @@ def main(argv=None) -> int:
         hist = arena.history(ids, spec.players, stream_records(spec, arena.device))  # this rank's hits
         for p in ids:
             print(json.dumps(dict(_timeline(hist, p), rank=rank)), flush=True)
+    if ladder_tracks and rank == 0:  # the roster is replicated after the last merge
+        for line in ladder_lines(roster, ladder_tracks, args.ladder_top, ladder_ids):
+            print(json.dumps(line), flush=True)
     if args.export_records:
         path = args.export_records + (".r%d" % rank if size > 1 else "")
         print(json.dumps({"exported": path, "bytes": arena.export(path), "rank": rank}), flush=True)
