@@ -7,6 +7,8 @@
 #include <cstdlib>
 #include <ATen/hip/HIPContext.h>
 
+#include <algorithm>
+#include <numeric>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -17,6 +19,7 @@
 #include "ingest.h"
 #include "kernels.h"
 #include "ladder_core.h"
+#include "matchmake_core.h"
 #include "select_core.h"
 
 namespace {
@@ -1029,6 +1032,137 @@ std::vector<Tensor> ladder(Tensor state, int64_t mask, int64_t score, double max
   return out;
 }
 
+// K12 (matchmake.hip; host mirror host.cpp): the roster operands every matchmaking call takes.
+// attrs may be absent ("no attributes"); returns its pointer or null.
+const float* matchmake_roster(const Tensor& state, const c10::optional<Tensor>& attrs, const Tensor& vst,
+                              const torch::Device& dev, const char* what) {
+  check(state, "state", torch::kFloat32, dev);
+  check(vst, "vst", torch::kFloat32, dev);
+  TORCH_CHECK(state.dim() == 2 && state.size(1) == ana::kRowFloats, what, ": state must be [P, 32]");
+  TORCH_CHECK(state.size(0) <= 0x7fffffffLL, what, ": P must be below 2^31");
+  TORCH_CHECK(vst.numel() == ana::kVstTiers, what, ": vst must have 31 entries (tiers -1..29)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(state.data_ptr()) % 16 == 0, what, ": state must be 16-B aligned");
+  if (!attrs.has_value() || !attrs->defined()) return nullptr;
+  check(*attrs, "attrs", torch::kFloat32, dev);
+  TORCH_CHECK(attrs->dim() == 2 && attrs->size(0) == state.size(0) && attrs->size(1) == 4, what,
+              ": attrs must be [P, 4]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(attrs->data_ptr()) % 16 == 0, what, ": attrs must be 16-B aligned");
+  return attrs->data_ptr<float>();
+}
+
+// packed rows [M, 4] int32: status, quality bits, p_win0 bits, 0 (ops/matchmake.py views them)
+Tensor preview(Tensor rec, int64_t K, Tensor state, c10::optional<Tensor> attrs, Tensor vst, double beta2,
+               double unknown_sigma) {
+  const auto dev = rec.device();
+  check(rec, "rec", torch::kInt32, dev);
+  TORCH_CHECK(K >= 1 && K <= ana::kSplitMaxK, "preview: K must be 1..5");
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == 2 * K + 2, "preview: rec must be [M, 2K+2]");
+  const float* at = matchmake_roster(state, attrs, vst, dev, "preview");
+  const int64_t M = rec.size(0), P = state.size(0);
+  Tensor out = torch::empty({M, (int64_t)ana::kPreviewWords}, rec.options());
+  if (M == 0) return out;
+  if (dev.is_cuda()) {
+    check_hip(ana::launch_preview((int)K, rec.data_ptr<int32_t>(), M, state.data_ptr<float>(), at,
+                                  vst.data_ptr<float>(), P, (float)beta2, (float)unknown_sigma,
+                                  out.data_ptr<int32_t>(), stream_of(rec)),
+              "preview");
+  } else {
+    TORCH_CHECK(ana::host_preview((int)K, rec.data_ptr<int32_t>(), M, state.data_ptr<float>(), at,
+                                  vst.data_ptr<float>(), P, (float)beta2, (float)unknown_sigma,
+                                  out.data_ptr<int32_t>()) == 0, "preview: bad arguments");
+  }
+  return out;
+}
+
+// [packed rows [L, 8] int32 (status, split, team0, quality, p_win0, quality_given bits, 0, 0),
+//  records [L, 2K+2] int32]
+std::vector<Tensor> balance(Tensor lobbies, int64_t K, Tensor state, c10::optional<Tensor> attrs, Tensor vst,
+                            int64_t mode, double beta2, double unknown_sigma) {
+  const auto dev = lobbies.device();
+  check(lobbies, "lobbies", torch::kInt32, dev);
+  TORCH_CHECK(K >= 1 && K <= ana::kSplitMaxK, "balance: K must be 1..5");
+  TORCH_CHECK(lobbies.dim() == 2 && lobbies.size(1) == 2 * K, "balance: lobbies must be [L, 2K]");
+  TORCH_CHECK(mode >= 0 && mode < ana::kModes, "balance: mode must be 0..5");
+  const float* at = matchmake_roster(state, attrs, vst, dev, "balance");
+  const int64_t L = lobbies.size(0), P = state.size(0);
+  Tensor out = torch::empty({L, (int64_t)ana::kBalanceWords}, lobbies.options());
+  Tensor records = torch::empty({L, 2 * K + 2}, lobbies.options());
+  if (L == 0) return {out, records};
+  if (dev.is_cuda()) {
+    check_hip(ana::launch_balance((int)K, lobbies.data_ptr<int32_t>(), L, state.data_ptr<float>(), at,
+                                  vst.data_ptr<float>(), P, (int)mode, (float)beta2, (float)unknown_sigma,
+                                  out.data_ptr<int32_t>(), records.data_ptr<int32_t>(), stream_of(lobbies)),
+              "balance");
+  } else {
+    TORCH_CHECK(ana::host_balance((int)K, lobbies.data_ptr<int32_t>(), L, state.data_ptr<float>(), at,
+                                  vst.data_ptr<float>(), P, (int)mode, (float)beta2, (float)unknown_sigma,
+                                  out.data_ptr<int32_t>(), records.data_ptr<int32_t>()) == 0,
+                "balance: bad arguments");
+  }
+  return {out, records};
+}
+
+// [keys, positions] int32 [Q]: the queue's sort keys in ascending order (descending prior mu,
+// kLadderUnranked = -1 last) and the queue positions in that order; stable
+std::vector<Tensor> queue_order(Tensor queue, Tensor state, c10::optional<Tensor> attrs, Tensor vst, int64_t mode,
+                                double unknown_sigma) {
+  const auto dev = queue.device();
+  check(queue, "queue", torch::kInt32, dev);
+  TORCH_CHECK(queue.dim() == 1 && queue.size(0) <= 0x7fffffffLL, "queue_order: queue must be [Q], Q < 2^31");
+  TORCH_CHECK(mode >= 0 && mode < ana::kModes, "queue_order: mode must be 0..5");
+  const float* at = matchmake_roster(state, attrs, vst, dev, "queue_order");
+  const int64_t Q = queue.size(0), P = state.size(0);
+  Tensor keys = torch::empty({Q}, queue.options()), vals = torch::empty({Q}, queue.options());
+  if (Q == 0) return {keys, vals};
+  auto u = [](Tensor& t) { return reinterpret_cast<uint32_t*>(t.data_ptr<int32_t>()); };
+  if (!dev.is_cuda()) {
+    TORCH_CHECK(ana::host_queue_keys(queue.data_ptr<int32_t>(), Q, state.data_ptr<float>(), at,
+                                     vst.data_ptr<float>(), P, (int)mode, (float)unknown_sigma, u(keys),
+                                     u(vals)) == 0, "queue_order: bad arguments");
+    Tensor sk = torch::empty({Q}, queue.options()), sv = torch::empty({Q}, queue.options());
+    const uint32_t* k = u(keys);
+    uint32_t* order = u(sv);
+    std::iota(order, order + Q, 0u);
+    std::stable_sort(order, order + Q, [&](uint32_t a, uint32_t b) { return k[a] < k[b]; });
+    for (int64_t i = 0; i < Q; ++i) u(sk)[i] = k[order[i]];
+    return {sk, sv};
+  }
+  const hipStream_t s = stream_of(queue);
+  check_hip(ana::launch_queue_keys(queue.data_ptr<int32_t>(), Q, state.data_ptr<float>(), at, vst.data_ptr<float>(),
+                                   P, (int)mode, (float)unknown_sigma, u(keys), u(vals), s),
+            "queue_keys");
+  Tensor kalt = torch::empty({Q}, queue.options()), valt = torch::empty({Q}, queue.options());
+  Tensor ws = torch::empty({(int64_t)ana::radix_sort_workspace_bytes(Q)}, queue.options().dtype(torch::kUInt8));
+  int in_alt = 0;
+  check_hip(ana::launch_radix_sort_pairs(u(keys), u(vals), u(kalt), u(valt), Q, 32, ws.data_ptr<uint8_t>(), &in_alt, s),
+            "queue_order (sort)");
+  if (in_alt) return {kalt, valt};
+  return {keys, vals};
+}
+
+// (lanes of a lane group, lobbies per wave, lobbies per workgroup) of preview / balance at team size K
+std::tuple<int64_t, int64_t, int64_t> matchmake_geometry(int64_t K) {
+  TORCH_CHECK(K >= 1 && K <= ana::kSplitMaxK, "K must be 1..5");
+  const int G = ana::split_group_lanes((int)K);
+  return {G, 64 / G, ana::kMatchmakeThreads / G};
+}
+
+std::vector<int64_t> split_masks(int64_t K) {
+  std::vector<int64_t> out;
+  auto fill = [&](const auto& t) {
+    for (uint16_t m : t.mask) out.push_back(m);
+  };
+  switch (K) {
+    case 1: fill(ana::kSplits<1>); break;
+    case 2: fill(ana::kSplits<2>); break;
+    case 3: fill(ana::kSplits<3>); break;
+    case 4: fill(ana::kSplits<4>); break;
+    case 5: fill(ana::kSplits<5>); break;
+    default: TORCH_CHECK(false, "K must be 1..5");
+  }
+  return out;
+}
+
 void reset_tags(Tensor state) {
   const auto dev = state.device();
   check(state, "state", torch::kFloat32, dev);
@@ -1110,6 +1244,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ladder", &ladder, "K11: [order, score, rank] per track of the mask (bit t = granule t) of a roster's state: "
         "descending score, ties by ascending id, rank -1 = unranked", py::arg("state"), py::arg("mask"),
         py::arg("score"), py::arg("max_sigma"));
+  m.def("preview", &preview, "K12: packed [M, 4] int32 rows (status, quality, p_win0 bits, 0) of a stream's records "
+        "against the stored roster: what rate would write, read-only", py::arg("rec"), py::arg("K"), py::arg("state"),
+        py::arg("attrs"), py::arg("vst"), py::arg("beta2"), py::arg("unknown_sigma"));
+  m.def("balance", &balance, "K12: [packed [L, 8] int32 rows (status, split, team0, quality, p_win0, quality_given), "
+        "records [L, 2K+2]] of the best split of each lobby", py::arg("lobbies"), py::arg("K"), py::arg("state"),
+        py::arg("attrs"), py::arg("vst"), py::arg("mode"), py::arg("beta2"), py::arg("unknown_sigma"));
+  m.def("queue_order", &queue_order, "K12: [sorted keys, queue positions] of a queue by descending mode-track prior mu "
+        "(stable; failed players last with key -1)", py::arg("queue"), py::arg("state"), py::arg("attrs"),
+        py::arg("vst"), py::arg("mode"), py::arg("unknown_sigma"));
+  m.def("matchmake_geometry", &matchmake_geometry, "K12: (lanes per lobby, lobbies per wave, lobbies per workgroup)");
+  m.def("split_masks", &split_masks, "K12: the team-0 masks of the splits of a 2K lobby, in index order");
   m.attr("LADDER_CONSERVATIVE") = (int)ana::kLadderConservative;
   m.attr("LADDER_MU") = (int)ana::kLadderMu;
   m.attr("HIT_WORDS") = ana::kHitWords;

@@ -13,6 +13,7 @@
 
 #include "gen_core.h"
 #include "ladder_core.h"
+#include "matchmake_core.h"
 #include "rate_core.h"
 #include "select_core.h"
 
@@ -345,6 +346,184 @@ int64_t host_ladder(const float* state, int64_t P, int track, int score, float m
     }
   }
   return R;
+}
+
+// K12: the device's preview per record, on rate_k's own code path (decode_record, the prior
+// loop in slot order, copy_dup_priors, match_quality) in fp64, so status and quality are the
+// bits host_rate writes; p_win0 from the same sums
+template <int K>
+static void preview_k(const int32_t* rec, int64_t M, const float* state, const float* attrs, const float* vst,
+                      int64_t P, double beta2, double us, int32_t* out) {
+  constexpr int S = 2 * K;
+  const float no_attr[4] = {NAN, NAN, NAN, 0.f};
+  for (int64_t m = 0; m < M; ++m) {
+    MatchWork<double, K> w;
+    decode_record<double, K>(rec + m * (S + 2), P, w);
+    double q = 0, pw = 0;
+    if (w.status == kRated) {
+      uint8_t st = kRated;
+      uint32_t nulls = 0;
+      for (int j = 0; j < S && st == kRated; ++j) {
+        if (w.first[j] != j) continue;
+        const float* row = state + (int64_t)w.id[j] * kRowFloats;
+        const float* gm = row + 4 * (1 + w.mode);
+        st = make_prior<double, K>(w, j, (double)row[0], (double)row[2], (double)gm[0], (double)gm[2],
+                                   attrs ? attrs + (int64_t)w.id[j] * 4 : no_attr, us, vst, nulls);
+      }
+      w.status = st;
+      if (st == kRated) {
+        copy_dup_priors<double, K>(w);
+        if (w.n0 == 0 || w.n1 == 0) {
+          w.status = kErrEmptyRoster;
+        } else {
+          q = match_quality<double, K>(w.mm, w.sm, w.n0, w.n1, beta2);
+          double s2 = 0, d = 0;
+          bool finite = true;
+          for (int j = 0; j < S; ++j) {
+            const bool in0 = j < K && j < w.n0, in1 = j >= K && j - K < w.n1;
+            if (!(in0 || in1)) continue;
+            s2 += w.sm[j] * w.sm[j];
+            d += in0 ? w.mm[j] : -w.mm[j];
+            finite = finite && prior_finite<double>(w.ms[j], w.ss[j], w.mm[j], w.sm[j]);
+          }
+          pw = win_probability<double>(d, (double)(w.n0 + w.n1) * beta2 + s2);
+          if (!finite || !isfinite(q) || !isfinite(pw)) w.status = kErrNumeric;
+        }
+      }
+    }
+    const bool rated = w.status == kRated, afkish = w.status == kAfk || w.status == kInvalidRosters;
+    const float qo = rated ? (float)q : afkish ? 0.f : NAN, po = rated ? (float)pw : NAN;
+    int32_t* o = out + m * kPreviewWords;
+    o[0] = (int32_t)w.status;
+    o[1] = (int32_t)ladder_bits(qo);
+    o[2] = (int32_t)ladder_bits(po);
+    o[3] = 0;
+  }
+}
+
+int host_preview(int K, const int32_t* rec, int64_t M, const float* state, const float* attrs, const float* vst,
+                 int64_t P, float beta2, float unknown_sigma, int32_t* out) {
+  if (M < 0 || P < 0 || P > 0x7fffffffll) return -1;
+  switch (K) {
+    case 1: preview_k<1>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); return 0;
+    case 2: preview_k<2>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); return 0;
+    case 3: preview_k<3>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); return 0;
+    case 4: preview_k<4>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); return 0;
+    case 5: preview_k<5>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); return 0;
+    default: return -1;
+  }
+}
+
+// fp32 player_prior of one player, as the device's load_prior
+static uint8_t host_prior(const float* state, const float* attrs, const float* vst, float us, int32_t id, int mode,
+                          float& ms, float& ss, float& mm, float& sm) {
+  const float no_attr[4] = {NAN, NAN, NAN, 0.f};
+  const float* row = state + (int64_t)id * kRowFloats;
+  const float* gm = row + 4 * (1 + mode);
+  uint32_t flags;
+  ms = ss = mm = sm = NAN;
+  float a, b, c, d;
+  const uint8_t st = player_prior<float>(row[0], row[2], gm[0], gm[2], attrs ? attrs + (int64_t)id * 4 : no_attr, us,
+                                         vst, a, b, c, d, flags);
+  if (st == kRated) {
+    ms = a;
+    ss = b;
+    mm = c;
+    sm = d;
+  }
+  return st;
+}
+
+// the split choice in fp32 (matchmake_core.h: the device's bits); quality and p_win0 in fp64
+template <int K>
+static void balance_k(const int32_t* lobbies, int64_t L, const float* state, const float* attrs, const float* vst,
+                      int64_t P, int mode, double beta2, float us, int32_t* out, int32_t* records) {
+  constexpr int S = 2 * K, C = split_count(K);
+  const int32_t meta0 = (int32_t)pack_meta0(mode, K, K, 2);
+  for (int64_t l = 0; l < L; ++l) {
+    const int32_t* ids = lobbies + l * S;
+    bool bad = false, e_seed = false, e_sigma = false, e_num = false;
+    for (int j = 0; j < S; ++j) {
+      if (ids[j] < 0 || (int64_t)ids[j] >= P) bad = true;
+      for (int i = 0; i < j; ++i)
+        if (ids[i] == ids[j]) bad = true;
+    }
+    float mu[S] = {};
+    double s2 = 0;
+    for (int j = 0; j < S && !bad; ++j) {
+      float ms, ss, mm, sm;
+      const uint8_t st = host_prior(state, attrs, vst, us, ids[j], mode, ms, ss, mm, sm);
+      e_seed = e_seed || st == kErrSeed;
+      e_sigma = e_sigma || st == kErrSigma;
+      e_num = e_num || !prior_finite<float>(ms, ss, mm, sm);
+      mu[j] = mm;
+      s2 += (double)sm * (double)sm;
+    }
+    uint32_t bb = 0xffffffffu, bi = 0;
+    for (int c = 0; c < C; ++c) {
+      const float d = split_d<K>(mu, kSplits<K>.mask[c]);
+      e_num = e_num || !isfinite(d);
+      if (split_abs_bits(d) < bb) {
+        bb = split_abs_bits(d);
+        bi = (uint32_t)c;
+      }
+    }
+    const uint32_t mask = kSplits<K>.mask[bi];
+    double db = 0, dg = 0;  // exact sums of the fp32 mus
+    for (int j = 0; j < S; ++j) {
+      db += ((mask >> j) & 1u) ? (double)mu[j] : -(double)mu[j];
+      dg += j < K ? (double)mu[j] : -(double)mu[j];
+    }
+    const double den = (double)S * beta2 + s2;
+    const double q = quality_from_sums<double>(S, s2, db, beta2), qg = quality_from_sums<double>(S, s2, dg, beta2);
+    const double pw = win_probability<double>(db, den);
+    const uint8_t st = bad ? kErrBadRecord
+                       : e_seed ? kErrSeed
+                       : e_sigma ? kErrSigma
+                       : (e_num || !isfinite((float)q) || !isfinite((float)qg) || !isfinite((float)pw)) ? kErrNumeric
+                                                                                                       : kRated;
+    const bool ok = st == kRated;
+    int32_t* o = out + l * kBalanceWords;
+    o[0] = (int32_t)st;
+    o[1] = ok ? (int32_t)bi : -1;
+    o[2] = ok ? (int32_t)mask : 0;
+    o[3] = (int32_t)ladder_bits(ok ? (float)q : NAN);
+    o[4] = (int32_t)ladder_bits(ok ? (float)pw : NAN);
+    o[5] = (int32_t)ladder_bits(ok ? (float)qg : NAN);
+    o[6] = o[7] = 0;
+    int32_t* r = records + l * (S + 2);
+    for (int j = 0; j < S; ++j) r[ok ? split_position(mask, j, K) : j] = ids[j];
+    r[S] = meta0;
+    r[S + 1] = 0;
+  }
+}
+
+int host_balance(int K, const int32_t* lobbies, int64_t L, const float* state, const float* attrs, const float* vst,
+                 int64_t P, int mode, float beta2, float unknown_sigma, int32_t* out, int32_t* records) {
+  if (L < 0 || P < 0 || P > 0x7fffffffll || mode < 0 || mode >= kModes) return -1;
+  switch (K) {
+    case 1: balance_k<1>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records); return 0;
+    case 2: balance_k<2>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records); return 0;
+    case 3: balance_k<3>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records); return 0;
+    case 4: balance_k<4>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records); return 0;
+    case 5: balance_k<5>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records); return 0;
+    default: return -1;
+  }
+}
+
+int host_queue_keys(const int32_t* queue, int64_t Q, const float* state, const float* attrs, const float* vst,
+                    int64_t P, int mode, float unknown_sigma, uint32_t* keys, uint32_t* vals) {
+  if (Q < 0 || Q > 0x7fffffffll || P < 0 || P > 0x7fffffffll || mode < 0 || mode >= kModes) return -1;
+  for (int64_t i = 0; i < Q; ++i) {
+    const int32_t id = queue[i];
+    keys[i] = kLadderUnranked;
+    vals[i] = (uint32_t)i;
+    if (id < 0 || (int64_t)id >= P) continue;
+    float ms, ss, mm, sm;
+    const uint8_t st = host_prior(state, attrs, vst, unknown_sigma, id, mode, ms, ss, mm, sm);
+    keys[i] = queue_key(st, mm);
+  }
+  return 0;
 }
 
 }  // namespace ana

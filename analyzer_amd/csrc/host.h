@@ -50,4 +50,14 @@ int64_t records_select_host(int K, const int32_t* rec, const float* rows, int64_
 // bit-identical to the device.  Returns R, the number of ranked players (-1: bad arguments).
 int64_t host_ladder(const float* state, int64_t P, int track, int score, float max_sigma, int32_t* order,
                     float* score_out, int32_t* rank);
+// K12 host mirror (matchmake_core.h); out / records as launch_preview / launch_balance /
+// launch_queue_keys (kernels.h) lay them out; attrs may be null.  preview runs rate's own
+// fp64 path (status and quality are the bits host_rate writes); balance chooses the split in
+// fp32, bit-identical to the device, and computes quality and p_win0 in fp64.  -1: bad arguments.
+int host_preview(int K, const int32_t* rec, int64_t M, const float* state, const float* attrs, const float* vst,
+                 int64_t P, float beta2, float unknown_sigma, int32_t* out);
+int host_balance(int K, const int32_t* lobbies, int64_t L, const float* state, const float* attrs, const float* vst,
+                 int64_t P, int mode, float beta2, float unknown_sigma, int32_t* out, int32_t* records);
+int host_queue_keys(const int32_t* queue, int64_t Q, const float* state, const float* attrs, const float* vst,
+                    int64_t P, int mode, float unknown_sigma, uint32_t* keys, uint32_t* vals);
 }  // namespace ana

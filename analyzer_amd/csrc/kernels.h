@@ -63,6 +63,27 @@ int launch_ladder_keys(const float* state, int64_t P, uint32_t mask, int score, 
 int launch_ladder_ranks(const uint32_t* keys, const uint32_t* ids, int64_t P, int64_t R, int32_t* order, float* score,
                         int32_t* rank, hipStream_t s);
 
+// K12 matchmaking (matchmake.hip, matchmake_core.h); the roster is only read.  state [P][32]
+// and attrs [P][4] 16-B aligned; attrs may be null ("no attributes": a NULL shared track is
+// then kErrSeed); vst: kVstTiers floats.
+// preview: per record of rec [M][2K+2] the packed row out [M][kPreviewWords] = status, quality
+// and p_win0 (fp32 bits), 0: what `rate` would write for the record against the stored state
+// (winner bits ignored), and team 0's win probability (NaN unless kRated).
+int launch_preview(int K, const int32_t* rec, int64_t M, const float* state, const float* attrs, const float* vst,
+                   int64_t P, float beta2, float unknown_sigma, int32_t* out, hipStream_t s);
+// balance: per lobby of lobbies [L][2K] (all slots filled) on mode 0..5 the packed row out
+// [L][kBalanceWords] = status, split index (-1 on error), team-0 mask (0), quality, p_win0,
+// quality_given (fp32 bits, NaN on error), 0, 0, and the stream record records [L][2K+2] of
+// the chosen split (on error: the ids as given).
+int launch_balance(int K, const int32_t* lobbies, int64_t L, const float* state, const float* attrs,
+                   const float* vst, int64_t P, int mode, float beta2, float unknown_sigma, int32_t* out,
+                   int32_t* records, hipStream_t s);
+// queue_keys: keys[i] = the descending-mu sort key of queue[i]'s mode-track prior
+// (kLadderUnranked: the prior fails or the id is outside [0, P)), vals[i] = i; sort the pairs
+// with launch_radix_sort_pairs (32 bits, stable: ties keep queue order)
+int launch_queue_keys(const int32_t* queue, int64_t Q, const float* state, const float* attrs, const float* vst,
+                      int64_t P, int mode, float unknown_sigma, uint32_t* keys, uint32_t* vals, hipStream_t s);
+
 // Stable LSD radix sort of (key, value) pairs on the low ``bits`` key bits
 // (radix_sort.hip).  Ping-pongs between the two buffer pairs; *result_in_alt
 // says which holds the result.  ws: radix_sort_workspace_bytes(n) bytes.

@@ -40,6 +40,8 @@ streams a long synthetic history through the engine window by window:
         --window 16000000 --records resident --history 17,4242 --export-records /data/records.bin
     python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
         --window 16000000 --ladder shared,ranked --ladder-top 10 --ladder-rank 17,4242
+    python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
+        --window 16000000 --matchmake ranked:3:100000
 """
 from __future__ import annotations
 
@@ -57,6 +59,7 @@ import torch
 from ..config import EngineConfig, RaterConfig
 from ..ops import rate as R
 from ..ops.ladder import build_ladder, track_index
+from ..ops.matchmake import make_lobbies, mode_index, preview_matches, queue_order
 from ..ops.synth import RosterSpec, StreamSpec, make_roster, make_stream
 from ..parallel.comm import broadcast_roster, init_from_env, reduce_counts, world
 from ..parallel.sweep import SweepMerger
@@ -431,6 +434,33 @@ def ladder_lines(roster: R.Roster, tracks, top: int = 10, ids=(), score: str = "
     return lines
 
 
+def matchmake_line(roster: R.Roster, mode: str, K: int, Q: int, seed: int = 2024) -> dict:
+    """One JSON-ready dict: ``make_lobbies`` (ops/matchmake.py) on ``roster`` for a queue of the
+    first Q players of a seeded ``torch.randperm(P)``: the lobbies formed, the unmatched players,
+    and what balancing bought -- mean and minimum quality, mean |p_win0 - 0.5| -- against the
+    lobbies as given (2K consecutive players of the descending-mu order, first K against last K)."""
+    S = 2 * K
+    gen = torch.Generator().manual_seed(int(seed))
+    queue = torch.randperm(roster.num_players, generator=gen)[:Q].to(torch.int32).to(roster.device)
+    bal, unmatched = make_lobbies(roster, queue, mode=mode, K=K)
+    ok = bal.status == 0
+    n = int(bal.status.numel())
+    line = {"matchmake": mode, "team_size": K, "queue": int(queue.numel()), "lobbies": n,
+            "balanced": int(ok.sum()), "unmatched": int(unmatched.numel())}
+    if int(ok.sum()):
+        # the lobbies as given, as stream records: their p_win0 comes from a preview
+        pos, _ = queue_order(roster, queue, mode)
+        given = bal.records.clone()
+        given[:, :S] = queue.index_select(0, pos[:n * S].to(torch.int64)).reshape(n, S)
+        p_given = preview_matches(roster, given).p_win0[ok].double()
+        q, qg = bal.quality[ok].double(), bal.quality_given[ok].double()
+        line.update(quality_given_mean=float(qg.mean()), quality_given_min=float(qg.min()),
+                    quality_mean=float(q.mean()), quality_min=float(q.min()),
+                    p_off_given_mean=float((p_given - 0.5).abs().mean()),
+                    p_off_mean=float((bal.p_win0[ok].double() - 0.5).abs().mean()))
+    return line
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--matches", type=float, required=True)
@@ -461,6 +491,9 @@ def main(argv=None) -> int:
     ap.add_argument("--ladder-top", type=int, default=10, metavar="K", help="with --ladder: the best K players")
     ap.add_argument("--ladder-rank", default=None, metavar="ID[,ID...]",
                     help="with --ladder: also the rank, score and percentile of these players")
+    ap.add_argument("--matchmake", default=None, metavar="MODE:K:Q",
+                    help="after the run, form balanced KvK lobbies on MODE from a queue of Q distinct players drawn "
+                         "with the run's seed, and print what balancing bought (one JSON line)")
     ap.add_argument("--sweeps", type=int, default=ecfg.sweeps, help="causal sweeps per window (N ranks)")
     ap.add_argument("--digests", action="store_true", help="print every window's digest")
     args = ap.parse_args(argv)
@@ -481,6 +514,16 @@ def main(argv=None) -> int:
         ap.error(str(e))
     if any(p < 0 or p >= spec.players for p in ladder_ids):
         ap.error("--ladder-rank ids must lie in [0, %d)" % spec.players)
+    mm = None
+    if args.matchmake:
+        try:
+            mode, k, q = args.matchmake.split(":")
+            mm = (mode, int(k), int(q))
+            mode_index(mode)
+            if not 1 <= mm[1] <= 5 or not 0 <= mm[2] <= spec.players:
+                raise ValueError("K must be 1..5 and Q 0..%d" % spec.players)
+        except ValueError as e:
+            ap.error("--matchmake MODE:K:Q: %s" % e)
     arena = None
     try:
         if resident:
@@ -529,6 +572,8 @@ def main(argv=None) -> int:
     if ladder_tracks and rank == 0:  # the roster is replicated after the last merge
         for line in ladder_lines(roster, ladder_tracks, args.ladder_top, ladder_ids):
             print(json.dumps(line), flush=True)
+    if mm is not None and rank == 0:
+        print(json.dumps(matchmake_line(roster, *mm, seed=spec.seed)), flush=True)
     if args.export_records:
         path = args.export_records + (".r%d" % rank if size > 1 else "")
         print(json.dumps({"exported": path, "bytes": arena.export(path), "rank": rank}), flush=True)
