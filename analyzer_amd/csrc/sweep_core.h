@@ -117,6 +117,9 @@ ANA_HD bool merged_ratio(float S, unsigned m, float& ratio, float& mdiv) {
   return false;
 }
 
+// neither +-inf nor NaN
+ANA_HD bool sweep_finite(float x) { return fabsf(x) <= 3.402823466e+38f; }
+
 // One track t of the decode: (amu, asg) the common window-start value of the track,
 // (a0mu, a0sg) the start's shared value, (dpi, dtau) the summed messages, touched the
 // summed touch count of the track.  Returns the decoded (mu, sigma).
@@ -133,12 +136,20 @@ ANA_HD bool merged_ratio(float S, unsigned m, float& ratio, float& mdiv) {
 // dynamics losses measured at Y's precision overshoot C's: 1 + sum r_pi -> 0 (-0.99
 // of C in one window for a player near sigma 100) and below.  The merge measures
 // every rank against the common start and keeps a wide margin (min 0.46-0.88).
+//
+// A summed message with a half that is not finite also counts as clamped, and the track
+// is left at its window-start value (a NULL track stays NULL): a +inf ratio would pass
+// the floor and write sigma = 0, an inf mean shift with a finite ratio mu = +-inf.  The
+// fp16 wire overflows at 65504, which r_tau = (pi / pi_B)(mu - mu_B) of a freshly seeded
+// player reaches (sigma 2000 -> 100 with a 300-point shift: 400 x 300), an N-rank sum
+// sooner.
 ANA_HD void sweep_apply_track(int t, float amu, float asg, float a0mu, float a0sg, float dpi, float dtau,
                               unsigned touched, bool seeded, float seed_mu, float seed_sig, bool scaled,
                               float& mu, float& sg, bool& clamped) {
   mu = amu;
   sg = asg;
-  clamped = false;
+  clamped = !(sweep_finite(dpi) && sweep_finite(dtau));
+  if (clamped) return;
   const bool live = amu == amu ? (dpi != 0.f || dtau != 0.f) : touched != 0u;
   if (!live) return;
   float bm, bs;

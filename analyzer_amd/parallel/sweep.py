@@ -81,7 +81,8 @@ MAX_RANKS = 15  # touch counts are base-16 fields in fp32 (see csrc/sweep_core.h
 
 class MergeClampError(FloatingPointError):
     """A decode's merged precision came out at or below zero (sweep_core.h
-    sweep_apply_track) and was held at the floor: the reference raises on numeric
+    sweep_apply_track) and was held at the floor, or its summed message was not finite
+    (an fp16 overflow) and the track was left at the window start: the reference raises on numeric
     trouble and dead-letters the batch (/root/reference/rater.py:7-8,
     worker.py:108-120); a silently clamped sigma must never be written."""
 BASE_FLOATS = 16  # base row: (mu, sigma) per 16-B granule of a roster row
@@ -783,7 +784,8 @@ class SweepMerger:
         if n:
             self.clamps.zero_()
             raise MergeClampError("sweep merge: %d decoded track(s) had a merged precision at or below zero "
-                                  "and were clamped (sigma x1000): the merged roster is not trustworthy"
+                                  "and were clamped (sigma x1000), or a summed message that is not finite "
+                                  "and were left at the window start: the merged roster is not trustworthy"
                                   % n)
 
     def stage_ms(self) -> Dict[str, float]:
