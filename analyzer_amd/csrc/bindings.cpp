@@ -1,7 +1,8 @@
 // PyTorch bindings of the engine.  Device (ROCm) tensors run the gfx950
-// kernels of kernels.hip on the current HIP stream; CPU tensors run the host
+// kernels (kernels.h) on the current HIP stream; CPU tensors run the host
 // mirror of host.cpp.  Every shape/dtype/device assumption a kernel makes is
-// checked here, on the host, before anything is launched.
+// checked here, on the host, before anything is launched, by the shared
+// operand checks below; an entry point is those and the device / host branch.
 #include <torch/extension.h>
 
 #include <cstdlib>
@@ -64,19 +65,73 @@ uint32_t u32(int64_t v, const char* name) {
   return (uint32_t)v;
 }
 
+// ---- operand checks shared by the entry points (common.h data layout); ``what`` names the
+// entry point in the message, and each returns what its caller needs next
+// match stream rec [M, 2K+2] int32 -> M
+int64_t check_rec(const Tensor& rec, int64_t K, const torch::Device& dev, const char* what) {
+  check(rec, "rec", torch::kInt32, dev);
+  TORCH_CHECK(K >= 1 && K <= ana::kMaxTeamSize, what, ": K (players per roster) must be 1..5");
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == 2 * K + 2, what, ": rec must be [M, 2K+2]");
+  return rec.size(0);
+}
+
+// roster state [P, 32] fp32 -> P
+int64_t check_state(const Tensor& state, const torch::Device& dev, const char* what) {
+  check(state, "state", torch::kFloat32, dev);
+  TORCH_CHECK(state.dim() == 2 && state.size(1) == ana::kRowFloats, what, ": state must be [P, 32]");
+  return state.size(0);
+}
+
+// player attributes [P, 4] fp32 -> their pointer
+const float* check_attrs(const Tensor& attrs, int64_t P, const torch::Device& dev, const char* what) {
+  check(attrs, "attrs", torch::kFloat32, dev);
+  TORCH_CHECK(attrs.dim() == 2 && attrs.size(0) == P && attrs.size(1) == 4, what, ": attrs must be [P, 4]");
+  return attrs.data_ptr<float>();
+}
+
+// the tier seed table, indexed by tier + 1 -> its pointer
+const float* check_vst(const Tensor& vst, const torch::Device& dev, const char* what) {
+  check(vst, "vst", torch::kFloat32, dev);
+  TORCH_CHECK(vst.numel() == ana::kVstTiers, what, ": vst must have 31 entries (tiers -1..29)");
+  return vst.data_ptr<float>();
+}
+
+// the schedule of rec: link [M, 2K] and deps [M], int32
+void check_schedule(const Tensor& link, const Tensor& deps, int64_t M, int64_t K, const torch::Device& dev) {
+  check(link, "link", torch::kInt32, dev);
+  check(deps, "deps", torch::kInt32, dev);
+  TORCH_CHECK(link.dim() == 2 && link.size(0) == M && link.size(1) == 2 * K, "link must be [M, 2K]");
+  TORCH_CHECK(deps.numel() == M, "deps must have M entries");
+}
+
+// the words of an int32 tensor as the kernels take them
+uint32_t* u32p(const Tensor& t) { return reinterpret_cast<uint32_t*>(t.data_ptr<int32_t>()); }
+
+bool present(const c10::optional<Tensor>& t) { return t.has_value() && t->defined() && t->numel() > 0; }
+
+int is_bf16(const Tensor& t) { return t.scalar_type() == torch::kBFloat16 ? 1 : 0; }
+
+// Stable sort of n uint32 (key, value) pairs by the low ``bits`` key bits (radix_sort.hip), in
+// place or into scratch buffers: returns the tensors that hold the result, {keys, vals}.
+std::vector<Tensor> sort_pairs_on_stream(Tensor keys, Tensor vals, int64_t n, int bits, hipStream_t s) {
+  Tensor kalt = torch::empty({n}, keys.options()), valt = torch::empty({n}, vals.options());
+  Tensor ws = torch::empty({(int64_t)ana::radix_sort_workspace_bytes(n)}, keys.options().dtype(torch::kUInt8));
+  int in_alt = 0;
+  check_hip(ana::launch_radix_sort_pairs(u32p(keys), u32p(vals), u32p(kalt), u32p(valt), n, bits,
+                                         ws.data_ptr<uint8_t>(), &in_alt, s),
+            "radix sort");
+  return in_alt ? std::vector<Tensor>{kalt, valt} : std::vector<Tensor>{keys, vals};
+}
+
 // --------------------------------------------------------------------- K7
 void gen_roster(Tensor state, Tensor attrs, int64_t seed, int64_t p_tier_null, int64_t p_tier_bad,
                 int64_t p_rp_ranked, int64_t p_rp_blitz, int64_t p_rated, int64_t p_mode_rated,
                 double mu_lo, double mu_span, double sig_lo, double sig_span) {
   const auto dev = state.device();
-  check(state, "state", torch::kFloat32, dev);
-  check(attrs, "attrs", torch::kFloat32, dev);
-  TORCH_CHECK(state.dim() == 2 && state.size(1) == ana::kRowFloats, "state must be [P, 32]");
-  TORCH_CHECK(attrs.dim() == 2 && attrs.size(1) == 4 && attrs.size(0) == state.size(0),
-              "attrs must be [P, 4]");
   ana::GenRosterParams g{};
   g.seed = (uint64_t)seed;
-  g.num_players = state.size(0);
+  g.num_players = check_state(state, dev, "gen_roster");
+  check_attrs(attrs, g.num_players, dev, "gen_roster");
   g.p_tier_null = u32(p_tier_null, "p_tier_null");
   g.p_tier_bad = u32(p_tier_bad, "p_tier_bad");
   g.p_rp_ranked = u32(p_rp_ranked, "p_rp_ranked");
@@ -100,9 +155,7 @@ void gen_stream(Tensor rec, int64_t K, int64_t seed, int64_t base, int64_t num_p
                 int64_t p_bad_rosters, int64_t p_tie, int64_t p_afk, int64_t p_hot,
                 int64_t hot_players, int64_t skew) {
   const auto dev = rec.device();
-  check(rec, "rec", torch::kInt32, dev);
-  TORCH_CHECK(K >= 1 && K <= 5, "K (players per roster slot block) must be 1..5");
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == 2 * K + 2, "rec must be [M, 2K+2]");
+  const int64_t M = check_rec(rec, K, dev, "gen_stream");
   TORCH_CHECK(team_size >= 1 && team_size <= K, "team_size must be in 1..K");
   TORCH_CHECK(num_players >= 1 && num_players < 0x7fffffffLL, "num_players out of range");
   TORCH_CHECK(hot_players >= 1 && hot_players <= num_players, "hot_players must be 1..num_players");
@@ -121,7 +174,6 @@ void gen_stream(Tensor rec, int64_t K, int64_t seed, int64_t base, int64_t num_p
   g.p_afk = u32(p_afk, "p_afk");
   g.p_hot = u32(p_hot, "p_hot");
   g.hot_players = u32(hot_players, "hot_players");
-  const int64_t M = rec.size(0);
   if (dev.is_cuda()) {
     check_hip(ana::launch_gen_stream((int)K, g, rec.data_ptr<int32_t>(), M, stream_of(rec)),
               "gen_stream");
@@ -145,27 +197,15 @@ std::vector<Tensor> sort_pairs(Tensor keys, Tensor vals, int64_t bits) {
   const int64_t n = keys.numel();
   TORCH_CHECK(vals.numel() == n, "keys and vals must have the same length");
   TORCH_CHECK(bits >= 1 && bits <= 32, "bits must be 1..32");
-  auto ka = keys.clone(), va = vals.clone();
-  auto kb = torch::empty_like(ka), vb = torch::empty_like(va);
-  auto ws = torch::empty({(int64_t)ana::radix_sort_workspace_bytes(n)},
-                         keys.options().dtype(torch::kUInt8));
-  int in_alt = 0;
-  auto u = [](Tensor& t) { return reinterpret_cast<uint32_t*>(t.data_ptr<int32_t>()); };
-  check_hip(ana::launch_radix_sort_pairs(u(ka), u(va), u(kb), u(vb), n, (int)bits,
-                                         ws.data_ptr<uint8_t>(), &in_alt, stream_of(keys)),
-            "sort_pairs");
-  return in_alt ? std::vector<Tensor>{kb, vb} : std::vector<Tensor>{ka, va};
+  return sort_pairs_on_stream(keys.clone(), vals.clone(), n, (int)bits, stream_of(keys));
 }
 
 // K5 host levelizer (conflict-free rounds for the exact DP mode).
 std::tuple<Tensor, int64_t> levels(Tensor rec, int64_t K, int64_t num_players) {
   TORCH_CHECK(!rec.is_cuda(), "levels runs on the host (pass a CPU stream)");
-  check(rec, "rec", torch::kInt32, rec.device());
-  TORCH_CHECK(K >= 1 && K <= 5, "K must be 1..5");
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == 2 * K + 2, "rec must be [M, 2K+2]");
-  auto level = torch::empty({rec.size(0)}, rec.options());
-  const int64_t depth = ana::host_levels((int)K, rec.data_ptr<int32_t>(), rec.size(0), num_players,
-                                         level.data_ptr<int32_t>());
+  const int64_t M = check_rec(rec, K, rec.device(), "levels");
+  auto level = torch::empty({M}, rec.options());
+  const int64_t depth = ana::host_levels((int)K, rec.data_ptr<int32_t>(), M, num_players, level.data_ptr<int32_t>());
   return {level, depth};
 }
 
@@ -174,24 +214,16 @@ std::tuple<Tensor, int64_t> levels_device(Tensor rec, int64_t K, int64_t num_pla
                                           Tensor deps) {
   const auto dev = rec.device();
   TORCH_CHECK(dev.is_cuda(), "levels_device runs on the device (host: levels)");
-  check(rec, "rec", torch::kInt32, dev);
-  check(link, "link", torch::kInt32, dev);
-  check(deps, "deps", torch::kInt32, dev);
-  TORCH_CHECK(K >= 1 && K <= 5, "K must be 1..5");
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == 2 * K + 2, "rec must be [M, 2K+2]");
-  const int64_t M = rec.size(0);
-  TORCH_CHECK(link.dim() == 2 && link.size(0) == M && link.size(1) == 2 * K, "link must be [M, 2K]");
-  TORCH_CHECK(deps.numel() == M, "deps must have M entries");
+  const int64_t M = check_rec(rec, K, dev, "levels_device");
+  check_schedule(link, deps, M, K, dev);
   TORCH_CHECK(M * 2 * K <= ana::kMaxSlots, "more than 2^28 slots in one window (split the stream)");
   TORCH_CHECK(num_players >= 1 && num_players < 0x7fffffffLL, "num_players out of range");
   auto level = torch::empty({M}, rec.options());
   auto pushed = torch::zeros({M}, rec.options());
   auto ctrl = torch::zeros({4}, rec.options());
-  check_hip(ana::launch_levels((int)K, rec.data_ptr<int32_t>(),
-                               reinterpret_cast<const uint32_t*>(link.data_ptr<int32_t>()),
-                               deps.data_ptr<int32_t>(), pushed.data_ptr<int32_t>(),
-                               level.data_ptr<int32_t>(), M, num_players,
-                               reinterpret_cast<uint32_t*>(ctrl.data_ptr<int32_t>()), stream_of(rec)),
+  check_hip(ana::launch_levels((int)K, rec.data_ptr<int32_t>(), u32p(link), deps.data_ptr<int32_t>(),
+                               pushed.data_ptr<int32_t>(), level.data_ptr<int32_t>(), M, num_players, u32p(ctrl),
+                               stream_of(rec)),
             "levels");
   const auto c = ctrl.cpu();
   TORCH_CHECK(c[3].item<int32_t>() == 0,
@@ -202,14 +234,8 @@ std::tuple<Tensor, int64_t> levels_device(Tensor rec, int64_t K, int64_t num_pla
 void schedule(Tensor rec, int64_t K, int64_t num_players, Tensor link, Tensor deps,
               Tensor workspace, Tensor ctrl, bool zero_ctrl, int64_t epoch_bump_ptr, int64_t sort_nt) {
   const auto dev = rec.device();
-  check(rec, "rec", torch::kInt32, dev);
-  check(link, "link", torch::kInt32, dev);
-  check(deps, "deps", torch::kInt32, dev);
-  TORCH_CHECK(K >= 1 && K <= 5, "K must be 1..5");
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == 2 * K + 2, "rec must be [M, 2K+2]");
-  const int64_t M = rec.size(0);
-  TORCH_CHECK(link.dim() == 2 && link.size(0) == M && link.size(1) == 2 * K, "link must be [M, 2K]");
-  TORCH_CHECK(deps.numel() == M, "deps must have M entries");
+  const int64_t M = check_rec(rec, K, dev, "schedule");
+  check_schedule(link, deps, M, K, dev);
   TORCH_CHECK(num_players >= 1 && num_players < 0x7fffffffLL, "num_players out of range");
   TORCH_CHECK(M * 2 * K <= ana::kMaxSlots, "more than 2^28 slots in one window (split the stream)");
   if (dev.is_cuda()) {
@@ -218,17 +244,13 @@ void schedule(Tensor rec, int64_t K, int64_t num_players, Tensor link, Tensor de
     TORCH_CHECK(ctrl.numel() >= 52, "ctrl must have 52 entries");
     const size_t need = ana::schedule_workspace_bytes(M * 2 * K, num_players);
     TORCH_CHECK((size_t)workspace.numel() >= need, "workspace too small: need ", need, " bytes");
-    check_hip(ana::launch_schedule((int)K, rec.data_ptr<int32_t>(), M, num_players,
-                                   reinterpret_cast<uint32_t*>(link.data_ptr<int32_t>()),
+    check_hip(ana::launch_schedule((int)K, rec.data_ptr<int32_t>(), M, num_players, u32p(link),
                                    deps.data_ptr<int32_t>(), workspace.data_ptr<uint8_t>(),
-                                   (size_t)workspace.numel(),
-                                   reinterpret_cast<uint32_t*>(ctrl.data_ptr<int32_t>()),
-                                   stream_of(rec), zero_ctrl,
+                                   (size_t)workspace.numel(), u32p(ctrl), stream_of(rec), zero_ctrl,
                                    reinterpret_cast<int32_t*>((intptr_t)epoch_bump_ptr), (int)sort_nt),
               "schedule");
   } else {
-    TORCH_CHECK(ana::host_schedule((int)K, rec.data_ptr<int32_t>(), M, num_players,
-                                   reinterpret_cast<uint32_t*>(link.data_ptr<int32_t>()),
+    TORCH_CHECK(ana::host_schedule((int)K, rec.data_ptr<int32_t>(), M, num_players, u32p(link),
                                    deps.data_ptr<int32_t>()) == 0,
                 "bad K");
   }
@@ -270,27 +292,18 @@ void rate(Tensor rec, int64_t K, Tensor link, Tensor deps, Tensor state, Tensor 
           int64_t chunk_len, bool ctrl_ready, std::vector<int64_t> knobs) {
   const auto dev = rec.device();
   TORCH_CHECK(knobs.size() == kKnobs, "knobs must be [idle, local, diag, tight, tele_fused_tail, tele_role]");
-  check(rec, "rec", torch::kInt32, dev);
-  check(state, "state", torch::kFloat32, dev);
-  check(attrs, "attrs", torch::kFloat32, dev);
-
-  check(vst, "vst", torch::kFloat32, dev);
-  TORCH_CHECK(K >= 1 && K <= 5, "K must be 1..5");
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == 2 * K + 2, "rec must be [M, 2K+2]");
-  const int64_t M = rec.size(0);
+  const int64_t M = check_rec(rec, K, dev, "rate");
   const int64_t S = 2 * K;
-  TORCH_CHECK(state.dim() == 2 && state.size(1) == ana::kRowFloats, "state must be [P, 32]");
-  const int64_t P = state.size(0);
+  const int64_t P = check_state(state, dev, "rate");
   TORCH_CHECK(P >= 1 && P * ana::kRowFloats * 4 < 0x7fffffffLL,
               "roster size out of range (<= 16.7M players per device roster)");
-  TORCH_CHECK(attrs.dim() == 2 && attrs.size(0) == P && attrs.size(1) == 4, "attrs must be [P, 4]");
+  check_attrs(attrs, P, dev, "rate");
   const int64_t qrow = check_rows_view(quality, "quality", torch::kFloat32, dev, M, 1);
   const int64_t srow = check_rows_view(status, "status", torch::kUInt8, dev, M, 1);
   const int64_t row = check_rows_view(s_mu, "s_mu", torch::kFloat32, dev, M, S);
   for (const Tensor* t : {&s_sig, &delta, &m_mu, &m_sig})
     TORCH_CHECK(check_rows_view(*t, "per-slot output", torch::kFloat32, dev, M, S) == row,
                 "per-slot outputs must share one row stride");
-  TORCH_CHECK(vst.numel() == ana::kVstTiers, "vst must have 31 entries (tiers -1..29)");
   float* fp = nullptr;
   if (record_first_prior) {
     check(first_prior, "first_prior", torch::kFloat32, dev);
@@ -310,7 +323,7 @@ void rate(Tensor rec, int64_t K, Tensor link, Tensor deps, Tensor state, Tensor 
   prm.epoch_ptr = reinterpret_cast<const int32_t*>((intptr_t)epoch_ptr);
   TORCH_CHECK(prm.epoch_ptr ? dev.is_cuda() : (epoch >= 1 && epoch <= 255), "epoch must be 1..255");
   prm.epoch = (int32_t)epoch;
-  prm.vst = vst.data_ptr<float>();
+  prm.vst = check_vst(vst, dev, "rate");
   prm.idle_spins = (int32_t)knobs[0];
   prm.local_handoff = (int32_t)knobs[1];
   prm.diag = (int32_t)knobs[2];
@@ -326,6 +339,7 @@ void rate(Tensor rec, int64_t K, Tensor link, Tensor deps, Tensor state, Tensor 
     check(link, "link", torch::kInt32, dev);
     check(deps, "deps", torch::kInt32, dev);
     check(ctrl, "ctrl", torch::kInt32, dev);
+    // (by word count, not check_schedule's [M, 2K]: any view of the schedule's link words is taken)
     TORCH_CHECK(link.numel() == M * S * ana::kLinkWords, "link must be [M, 2K]");
     TORCH_CHECK(deps.numel() == M, "deps must have M entries");
     TORCH_CHECK(ctrl.numel() >= 52, "ctrl must have 52 entries");
@@ -343,11 +357,8 @@ void rate(Tensor rec, int64_t K, Tensor link, Tensor deps, Tensor state, Tensor 
       out = ana::RateOut{b + 5 * S, reinterpret_cast<uint8_t*>(b + 5 * S + 1), b, b + S, b + 2 * S,
                          b + 3 * S, b + 4 * S, W, W, W * 4};
     }
-    const int rc = ana::launch_rate((int)K, rec.data_ptr<int32_t>(),
-                                    reinterpret_cast<const uint32_t*>(link.data_ptr<int32_t>()),
-                                    deps.data_ptr<int32_t>(), state.data_ptr<float>(),
-                                    attrs.data_ptr<float>(), fp, out,
-                                    reinterpret_cast<uint32_t*>(ctrl.data_ptr<int32_t>()), prm, tp,
+    const int rc = ana::launch_rate((int)K, rec.data_ptr<int32_t>(), u32p(link), deps.data_ptr<int32_t>(),
+                                    state.data_ptr<float>(), attrs.data_ptr<float>(), fp, out, u32p(ctrl), prm, tp,
                                     (int)blocks, stream_of(rec));
     check_hip(rc, "rate");
     if (!packed) {
@@ -388,11 +399,9 @@ Tensor gen_event_counts(int64_t M, int64_t seed, int64_t min_events, int64_t max
 void gen_events(Tensor rec, int64_t K, Tensor evoff, int64_t seed, int64_t min_events,
                 int64_t max_events, int64_t base, Tensor events) {
   const auto dev = rec.device();
-  check(rec, "rec", torch::kInt32, dev);
+  const int64_t M = check_rec(rec, K, dev, "gen_events");
   check(evoff, "evoff", torch::kInt64, dev);
   check(events, "events", torch::kInt32, dev);
-  TORCH_CHECK(K >= 1 && K <= 5 && rec.dim() == 2 && rec.size(1) == 2 * K + 2, "rec must be [M, 2K+2]");
-  const int64_t M = rec.size(0);
   TORCH_CHECK(evoff.numel() == M + 1, "evoff must have M + 1 entries");
   TORCH_CHECK(events.dim() == 2 && events.size(1) == 2, "events must be [E, 2] (8-B events, telemetry_core.h)");
   ana::GenEventParams g{(uint64_t)seed, (int32_t)min_events, (int32_t)max_events};
@@ -409,7 +418,7 @@ void gen_events(Tensor rec, int64_t K, Tensor evoff, int64_t seed, int64_t min_e
 // standalone aggregation; bad (device: int32[>=1] counter, host: ignored) counts malformed events
 int64_t telemetry(Tensor evoff, Tensor events, int64_t K, Tensor stats, Tensor bad) {
   const auto dev = events.device();
-  TORCH_CHECK(K >= 1 && K <= 5, "K must be 1..5");
+  TORCH_CHECK(K >= 1 && K <= ana::kMaxTeamSize, "telemetry: K must be 1..5");
   const int64_t M = evoff.numel() - 1;
   TORCH_CHECK(M >= 0, "evoff must have M + 1 entries");
   // standalone: the fused-executor knobs do not apply
@@ -418,8 +427,7 @@ int64_t telemetry(Tensor evoff, Tensor events, int64_t K, Tensor stats, Tensor b
   if (dev.is_cuda()) {
     check(bad, "bad", torch::kInt32, dev);
     TORCH_CHECK(bad.numel() >= 1, "bad must have an entry");
-    const int rc = ana::launch_telemetry((int)K, tp, reinterpret_cast<uint32_t*>(bad.data_ptr<int32_t>()),
-                                         stream_of(events));
+    const int rc = ana::launch_telemetry((int)K, tp, u32p(bad), stream_of(events));
     TORCH_CHECK(rc != (int)hipErrorNotSupported,
                 "ANA_TELE_DEBUG / ANA_TELE_SPAN select diagnostic telemetry variants, which only the "
                 "diagnostic library has: python -m analyzer_amd.build_ext --diag, then "
@@ -437,6 +445,15 @@ void check_rows(const Tensor& t, const char* name, int64_t P, int64_t cols, cons
   TORCH_CHECK(t.dim() == 2 && t.size(0) == P && t.size(1) == cols, name, " must be [P, ", cols, "]");
 }
 
+// the operands every K9 merge entry point takes: the window start s0 (base rows), the player
+// attributes and the tier seed table, for a roster of P players on dev -> vst's pointer
+const float* check_sweep(const Tensor& s0, const Tensor& attrs, const Tensor& vst, int64_t P,
+                         const torch::Device& dev, const char* what) {
+  check_rows(s0, "s0 (base rows)", P, ana::kBaseFloats, dev);
+  check_attrs(attrs, P, dev, what);
+  return check_vst(vst, dev, what);
+}
+
 // s0: common window start, prior: this rank's prior of the sweep (s0 itself in
 // the first sweep), s: the posterior after the local shard
 // K9 merge: s0 / prior / s2 are base rows [P, 16] = (mu, sigma) of the 8 granules
@@ -445,31 +462,27 @@ void sweep_delta(Tensor s0, Tensor prior, Tensor s, Tensor attrs, Tensor vst, do
                  bool scaled, Tensor buf) {
   const auto dev = s.device();
   const int64_t P = s.size(0);
-  check_rows(s0, "s0 (base rows)", P, ana::kBaseFloats, dev);
+  const float* vp = check_sweep(s0, attrs, vst, P, dev, "sweep_delta");
   check_rows(prior, "prior (base rows)", P, ana::kBaseFloats, dev);
   check_rows(s, "state", P, ana::kRowFloats, dev);
-  check_rows(attrs, "attrs", P, 4, dev);
   check_rows(buf, "buf", P, 16, dev);
-  check(vst, "vst", torch::kFloat32, dev);
-  TORCH_CHECK(vst.numel() == ana::kVstTiers, "vst must have 31 entries");
   if (dev.is_cuda()) {
     check_hip(ana::launch_sweep_delta(s0.data_ptr<float>(), prior.data_ptr<float>(),
-                                      s.data_ptr<float>(), attrs.data_ptr<float>(),
-                                      vst.data_ptr<float>(), (float)unknown_sigma, scaled ? 1 : 0,
+                                      s.data_ptr<float>(), attrs.data_ptr<float>(), vp,
+                                      (float)unknown_sigma, scaled ? 1 : 0,
                                       buf.data_ptr<float>(), P, stream_of(s)), "sweep_delta");
   } else {
     ana::host_sweep_delta(s0.data_ptr<float>(), prior.data_ptr<float>(), s.data_ptr<float>(),
-                          attrs.data_ptr<float>(), vst.data_ptr<float>(), (float)unknown_sigma,
-                          scaled, buf.data_ptr<float>(), P);
+                          attrs.data_ptr<float>(), vp, (float)unknown_sigma, scaled, buf.data_ptr<float>(), P);
   }
 }
 
 // clamps: int32 [1] (empty: not counted) += the decoded tracks whose merged precision
 // hit the floor (sweep_core.h sweep_apply_track); the merger raises on it
 static uint32_t* clamp_ptr(const c10::optional<Tensor>& c, const torch::Device& dev) {
-  if (!c.has_value() || !c->defined() || c->numel() == 0) return nullptr;
+  if (!present(c)) return nullptr;
   check(*c, "clamps", torch::kInt32, dev);
-  return reinterpret_cast<uint32_t*>(c->data_ptr<int32_t>());
+  return u32p(*c);
 }
 
 // decoded rows to s and, if s2 is non-empty, base rows [P, 16] (sweep_core.h) to s2
@@ -478,26 +491,21 @@ void sweep_apply(Tensor s0, Tensor buf, Tensor attrs, Tensor s, Tensor s2, Tenso
   const auto dev = s.device();
   uint32_t* cl = clamp_ptr(clamps, dev);
   const int64_t P = s.size(0);
-  check_rows(s0, "s0 (base rows)", P, ana::kBaseFloats, dev);
+  const float* vp = check_sweep(s0, attrs, vst, P, dev, "sweep_apply");
   check_rows(buf, "buf", P, 16, dev);
-  check_rows(attrs, "attrs", P, 4, dev);
   check_rows(s, "state", P, ana::kRowFloats, dev);
   float* p2 = nullptr;
   if (s2.numel()) {
     check_rows(s2, "s2 (base rows)", P, ana::kBaseFloats, dev);
     p2 = s2.data_ptr<float>();
   }
-  check(vst, "vst", torch::kFloat32, dev);
-  TORCH_CHECK(vst.numel() == ana::kVstTiers, "vst must have 31 entries");
   if (dev.is_cuda()) {
     check_hip(ana::launch_sweep_apply(s0.data_ptr<float>(), buf.data_ptr<float>(),
-                                      attrs.data_ptr<float>(), s.data_ptr<float>(), p2,
-                                      vst.data_ptr<float>(), (float)unknown_sigma, scaled ? 1 : 0, P, cl,
-                                      stream_of(s)), "sweep_apply");
+                                      attrs.data_ptr<float>(), s.data_ptr<float>(), p2, vp,
+                                      (float)unknown_sigma, scaled ? 1 : 0, P, cl, stream_of(s)), "sweep_apply");
   } else {
     ana::host_sweep_apply(s0.data_ptr<float>(), buf.data_ptr<float>(), attrs.data_ptr<float>(),
-                          s.data_ptr<float>(), p2, scaled, vst.data_ptr<float>(),
-                          (float)unknown_sigma, P, cl);
+                          s.data_ptr<float>(), p2, scaled, vp, (float)unknown_sigma, P, cl);
   }
 }
 
@@ -529,26 +537,21 @@ void sweep_delta_packed(Tensor s0, Tensor prior, Tensor s, Tensor attrs, Tensor 
                         Tensor msg, Tensor cnt) {
   const auto dev = s.device();
   const int64_t P = s.size(0);
-  check_rows(s0, "s0 (base rows)", P, ana::kBaseFloats, dev);
+  const float* vp = check_sweep(s0, attrs, vst, P, dev, "sweep_delta_packed");
   check_rows(prior, "prior (base rows)", P, ana::kBaseFloats, dev);
   check_rows(s, "state", P, ana::kRowFloats, dev);
-  check_rows(attrs, "attrs", P, 4, dev);
   check_operands(msg, cnt, P, dev);
-  check(vst, "vst", torch::kFloat32, dev);
-  TORCH_CHECK(vst.numel() == ana::kVstTiers, "vst must have 31 entries");
   if (dev.is_cuda()) {
     check_hip(ana::launch_sweep_delta_packed(s0.data_ptr<float>(), prior.data_ptr<float>(), s.data_ptr<float>(),
-                                             attrs.data_ptr<float>(), vst.data_ptr<float>(), (float)unknown_sigma,
-                                             msg.scalar_type() == torch::kBFloat16 ? 1 : 0, msg.data_ptr(),
-                                             cnt.data_ptr<int32_t>(), P, stream_of(s), msg.stride(0) / 2,
-                                             cnt.stride(0)),
+                                             attrs.data_ptr<float>(), vp, (float)unknown_sigma, is_bf16(msg),
+                                             msg.data_ptr(), cnt.data_ptr<int32_t>(), P, stream_of(s),
+                                             msg.stride(0) / 2, cnt.stride(0)),
               "sweep_delta_packed");
     return;
   }
   Tensor buf = torch::empty({P, 16}, s.options());
   ana::host_sweep_delta(s0.data_ptr<float>(), prior.data_ptr<float>(), s.data_ptr<float>(),
-                        attrs.data_ptr<float>(), vst.data_ptr<float>(), (float)unknown_sigma, true,
-                        buf.data_ptr<float>(), P);
+                        attrs.data_ptr<float>(), vp, (float)unknown_sigma, true, buf.data_ptr<float>(), P);
   msg.copy_(buf.slice(1, 0, 14));
   cnt.copy_(pack_touch(buf.slice(1, 14, 16)));
 }
@@ -561,18 +564,15 @@ void sweep_apply_packed(Tensor s0, Tensor msg, Tensor cnt, Tensor attrs, Tensor 
   const auto dev = s.device();
   uint32_t* cl = clamp_ptr(clamps, dev);
   const int64_t P = s.size(0);
-  check_rows(s0, "s0 (base rows)", P, ana::kBaseFloats, dev);
+  const float* vp = check_sweep(s0, attrs, vst, P, dev, "sweep_apply_packed");
   check_operands(msg, cnt, P, dev);
-  check_rows(attrs, "attrs", P, 4, dev);
   check_rows(s, "state", P, ana::kRowFloats, dev);
   float* p2 = nullptr;
   if (s2.numel()) {
     check_rows(s2, "s2 (base rows)", P, ana::kBaseFloats, dev);
     p2 = s2.data_ptr<float>();
   }
-  check(vst, "vst", torch::kFloat32, dev);
-  TORCH_CHECK(vst.numel() == ana::kVstTiers, "vst must have 31 entries");
-  const bool with_prefix = prefix.has_value() && prefix->defined() && prefix->numel() > 0;
+  const bool with_prefix = present(prefix);
   if (with_prefix) {
     TORCH_CHECK(delta.has_value() && delta->defined(), "a prefix needs a delta table");
     TORCH_CHECK(prefix->scalar_type() == msg.scalar_type() && prefix->is_contiguous() && prefix->device() == dev &&
@@ -582,9 +582,8 @@ void sweep_apply_packed(Tensor s0, Tensor msg, Tensor cnt, Tensor attrs, Tensor 
   }
   if (dev.is_cuda()) {
     check_hip(ana::launch_sweep_apply_packed(s0.data_ptr<float>(), msg.data_ptr(), cnt.data_ptr<int32_t>(),
-                                             msg.scalar_type() == torch::kBFloat16 ? 1 : 0,
-                                             attrs.data_ptr<float>(), s.data_ptr<float>(), p2,
-                                             vst.data_ptr<float>(), (float)unknown_sigma, P, cl,
+                                             is_bf16(msg), attrs.data_ptr<float>(), s.data_ptr<float>(), p2, vp,
+                                             (float)unknown_sigma, P, cl,
                                              with_prefix ? prefix->data_ptr() : nullptr,
                                              with_prefix ? delta->data_ptr<float>() : nullptr, stream_of(s),
                                              msg.stride(0) / 2, cnt.stride(0)),
@@ -597,7 +596,7 @@ void sweep_apply_packed(Tensor s0, Tensor msg, Tensor cnt, Tensor attrs, Tensor 
   buf.slice(1, 0, 14).copy_(msg);
   buf.slice(1, 14, 16).copy_(unpack_touch(cnt));
   ana::host_sweep_apply(s0.data_ptr<float>(), buf.data_ptr<float>(), attrs.data_ptr<float>(),
-                        s.data_ptr<float>(), p2, true, vst.data_ptr<float>(), (float)unknown_sigma, P, cl);
+                        s.data_ptr<float>(), p2, true, vp, (float)unknown_sigma, P, cl);
 }
 
 // the split collective's owner reduce (sweep.hip): recv [N * blk, 8] int32 words of
@@ -612,7 +611,7 @@ void sweep_block_reduce(Tensor recv, int64_t N, bool bf16, Tensor total, const c
   const int64_t blk = recv.size(0) / N;
   TORCH_CHECK(total.dim() == 2 && total.size(0) == blk && total.size(1) == 8, "total must be [blk, 8]");
   int32_t* pp = nullptr;
-  if (pref.has_value() && pref->defined() && pref->numel()) {
+  if (present(pref)) {
     check(*pref, "pref", torch::kInt32, dev);
     TORCH_CHECK(pref->dim() == 2 && pref->size(0) == N * blk && pref->size(1) == 7, "pref must be [N * blk, 7]");
     pp = pref->data_ptr<int32_t>();
@@ -626,9 +625,7 @@ void sweep_block_reduce(Tensor recv, int64_t N, bool bf16, Tensor total, const c
 // packed [M, row] += delta [P, 16] fp32 (raw natural-parameter increments per track)
 void correct_records(Tensor rec, int64_t K, Tensor rows, Tensor delta) {
   const auto dev = rows.device();
-  check(rec, "rec", torch::kInt32, dev);
-  TORCH_CHECK(K >= 1 && K <= 5 && rec.dim() == 2 && rec.size(1) == 2 * K + 2, "rec must be [M, 2K+2]");
-  const int64_t M = rec.size(0);
+  const int64_t M = check_rec(rec, K, dev, "correct_records");
   TORCH_CHECK(rows.dim() == 2 && rows.size(0) == M && rows.scalar_type() == torch::kFloat32 && rows.stride(1) == 1 &&
                   rows.size(1) >= 5 * 2 * K + 2,
               "rows must be RateResult.packed [M, row] fp32");
@@ -649,24 +646,21 @@ void correct_records(Tensor rec, int64_t K, Tensor rows, Tensor delta) {
 void prefix_delta(Tensor s0, Tensor prefix, Tensor attrs, Tensor vst, double unknown_sigma, Tensor delta) {
   const auto dev = s0.device();
   const int64_t P = s0.size(0);
-  check_rows(s0, "s0 (base rows)", P, ana::kBaseFloats, dev);
-  check_rows(attrs, "attrs", P, 4, dev);
+  const float* vp = check_sweep(s0, attrs, vst, P, dev, "prefix_delta");
   check_rows(delta, "delta", P, 16, dev);
-  check(vst, "vst", torch::kFloat32, dev);
   TORCH_CHECK(prefix.device() == dev && prefix.is_contiguous() && prefix.dim() == 2 && prefix.size(0) == P &&
                   prefix.size(1) == 14 &&
                   (prefix.scalar_type() == torch::kBFloat16 || prefix.scalar_type() == torch::kHalf),
               "prefix must be a contiguous bf16 / fp16 [P, 14]");
   if (dev.is_cuda()) {
-    check_hip(ana::launch_prefix_delta(s0.data_ptr<float>(), prefix.data_ptr(),
-                                       prefix.scalar_type() == torch::kBFloat16 ? 1 : 0, attrs.data_ptr<float>(),
-                                       vst.data_ptr<float>(), (float)unknown_sigma, delta.data_ptr<float>(), P,
+    check_hip(ana::launch_prefix_delta(s0.data_ptr<float>(), prefix.data_ptr(), is_bf16(prefix),
+                                       attrs.data_ptr<float>(), vp, (float)unknown_sigma, delta.data_ptr<float>(), P,
                                        stream_of(s0)),
               "prefix_delta");
     return;
   }
   Tensor pf = prefix.to(torch::kFloat32).contiguous();
-  ana::host_prefix_delta(s0.data_ptr<float>(), pf.data_ptr<float>(), attrs.data_ptr<float>(), vst.data_ptr<float>(),
+  ana::host_prefix_delta(s0.data_ptr<float>(), pf.data_ptr<float>(), attrs.data_ptr<float>(), vp,
                          (float)unknown_sigma, delta.data_ptr<float>(), P);
 }
 
@@ -675,104 +669,55 @@ void prefix_delta(Tensor s0, Tensor prefix, Tensor attrs, Tensor vst, double unk
 // (any row stride); out: [cap, 33] float entries, cap >= m * 2K
 void pack_rows(Tensor rec, int64_t K, Tensor status, Tensor state, Tensor out) {
   const auto dev = state.device();
-  check(rec, "rec", torch::kInt32, dev);
-  check(state, "state", torch::kFloat32, dev);
+  const int64_t m = check_rec(rec, K, dev, "pack_rows");
+  const int64_t P = check_state(state, dev, "pack_rows");
   check(out, "out", torch::kFloat32, dev);
-  TORCH_CHECK(K >= 1 && K <= 5 && rec.dim() == 2 && rec.size(1) == 2 * K + 2, "rec must be [m, 2K+2]");
-  const int64_t m = rec.size(0);
-  TORCH_CHECK(state.dim() == 2 && state.size(1) == ana::kRowFloats, "state must be [P, 32]");
   TORCH_CHECK(out.dim() == 2 && out.size(1) == 33 && out.size(0) >= m * 2 * K, "out must be [cap >= m*2K, 33]");
   const int64_t sstride = check_rows_view(status, "status", torch::kUInt8, dev, m, 1);
-  const int64_t P = state.size(0);
   if (dev.is_cuda()) {
     check_hip(ana::launch_pack_rows(rec.data_ptr<int32_t>(), (int)K, m, status.data_ptr<uint8_t>(), sstride,
                                     state.data_ptr<float>(), out.data_ptr<float>(), out.size(0),
                                     stream_of(state)), "pack_rows");
     return;
   }
-  const int S = 2 * (int)K;
-  const int32_t* r = rec.data_ptr<int32_t>();
-  const uint8_t* st = status.data_ptr<uint8_t>();
-  const float* sp = state.data_ptr<float>();
-  float* o = out.data_ptr<float>();
-  for (int64_t e = 0; e < out.size(0); ++e) {
-    int32_t id = -1;
-    if (e < m * S) {
-      const int64_t i = e / S;
-      const int j = (int)(e % S);
-      const uint32_t m0 = (uint32_t)r[i * (S + 2) + S];
-      const int n = j < K ? (int)ana::meta_n0(m0) : (int)ana::meta_n1(m0);
-      const int32_t v = r[i * (S + 2) + j];
-      if (st[i * sstride] == ana::kRated && (j < K ? j : j - K) < n && v >= 0 && v < P) id = v;
-    }
-    if (id >= 0)
-      for (int k = 0; k < ana::kRowFloats; ++k) o[e * 33 + k] = sp[(int64_t)id * ana::kRowFloats + k];
-    int32_t* oi = reinterpret_cast<int32_t*>(o + e * 33 + 32);
-    *oi = id;
-  }
+  TORCH_CHECK(ana::host_pack_rows(rec.data_ptr<int32_t>(), (int)K, m, status.data_ptr<uint8_t>(), sstride,
+                                  state.data_ptr<float>(), P, out.data_ptr<float>(), out.size(0)) == 0, "bad K");
 }
 
 // C2 race detector: rec [M, 2K+2] (the window), idx int64 [m] (one round's matches),
 // owner int64 [P] (zeroed once per window), flag int32 [1]
 void check_round(Tensor rec, int64_t K, Tensor idx, int64_t round, Tensor owner, Tensor flag) {
   const auto dev = rec.device();
-  check(rec, "rec", torch::kInt32, dev);
+  check_rec(rec, K, dev, "check_round");
   check(idx, "idx", torch::kInt64, dev);
   check(owner, "owner", torch::kInt64, dev);
   check(flag, "flag", torch::kInt32, dev);
-  TORCH_CHECK(K >= 1 && K <= 5 && rec.dim() == 2 && rec.size(1) == 2 * K + 2, "rec must be [M, 2K+2]");
   TORCH_CHECK(round >= 0 && round < 0xffffffffLL, "round out of range");
   const int64_t m = idx.numel(), P = owner.numel();
   if (dev.is_cuda()) {
     check_hip(ana::launch_check_round(rec.data_ptr<int32_t>(), (int)K, idx.data_ptr<int64_t>(), m, P,
                                       (uint32_t)round,
                                       reinterpret_cast<unsigned long long*>(owner.data_ptr<int64_t>()),
-                                      reinterpret_cast<uint32_t*>(flag.data_ptr<int32_t>()), stream_of(rec)),
+                                      u32p(flag), stream_of(rec)),
               "check_round");
     return;
   }
-  const int S = 2 * (int)K;
-  const int32_t* rp = rec.data_ptr<int32_t>();
-  const int64_t* ip = idx.data_ptr<int64_t>();
-  uint64_t* own = reinterpret_cast<uint64_t*>(owner.data_ptr<int64_t>());
-  int32_t* fl = flag.data_ptr<int32_t>();
-  for (int64_t i = 0; i < m; ++i) {
-    const int32_t* r = rp + ip[i] * (S + 2);
-    if (ana::early_status_k(r, S, P) != ana::kRated) continue;
-    const uint32_t m0 = (uint32_t)r[S];
-    const uint64_t mine = ((uint64_t)(round + 1) << 32) | (uint64_t)(ip[i] + 1);
-    for (int j = 0; j < S; ++j) {
-      const int n = j < K ? (int)ana::meta_n0(m0) : (int)ana::meta_n1(m0);
-      const int32_t p = r[j];
-      if ((j < K ? j : j - K) >= n || p < 0 || p >= P) continue;
-      if ((uint32_t)(own[p] >> 32) == (uint32_t)(round + 1)) {
-        if (own[p] != mine) fl[0] |= 1;
-      } else {
-        own[p] = mine;
-      }
-    }
-  }
+  TORCH_CHECK(ana::host_check_round(rec.data_ptr<int32_t>(), (int)K, idx.data_ptr<int64_t>(), m, P, (uint32_t)round,
+                                    reinterpret_cast<uint64_t*>(owner.data_ptr<int64_t>()),
+                                    flag.data_ptr<int32_t>()) == 0, "bad K");
 }
 
 void unpack_rows(Tensor buf, Tensor state) {
   const auto dev = state.device();
   check(buf, "buf", torch::kFloat32, dev);
-  check(state, "state", torch::kFloat32, dev);
   TORCH_CHECK(buf.dim() == 2 && buf.size(1) == 33, "buf must be [n, 33]");
-  TORCH_CHECK(state.dim() == 2 && state.size(1) == ana::kRowFloats, "state must be [P, 32]");
-  const int64_t n = buf.size(0), P = state.size(0);
+  const int64_t n = buf.size(0), P = check_state(state, dev, "unpack_rows");
   if (dev.is_cuda()) {
     check_hip(ana::launch_unpack_rows(buf.data_ptr<float>(), n, state.data_ptr<float>(), stream_of(state)),
               "unpack_rows");
     return;
   }
-  const float* b = buf.data_ptr<float>();
-  float* sp = state.data_ptr<float>();
-  for (int64_t e = 0; e < n; ++e) {
-    const int32_t id = *reinterpret_cast<const int32_t*>(b + e * 33 + 32);
-    if (id < 0 || id >= P) continue;
-    for (int k = 0; k < ana::kRowFloats; ++k) sp[(int64_t)id * ana::kRowFloats + k] = (k & 1) ? 0.f : b[e * 33 + k];
-  }
+  ana::host_unpack_rows(buf.data_ptr<float>(), n, state.data_ptr<float>(), P);
 }
 
 // A HIP stream restricted to ``num_cus`` compute units, spread evenly over the
@@ -842,9 +787,8 @@ bool can_wait_value(int64_t device) {
 
 // ------------------------------------------------------------------ ingest (P3)
 void write_record_file(const std::string& path, Tensor rec, int64_t K) {
-  check(rec, "rec", torch::kInt32, torch::Device(torch::kCPU));
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == 2 * K + 2, "rec must be [M, 2K+2]");
-  ana::write_record_file(path, rec.data_ptr<int32_t>(), rec.size(0), (int)K);
+  const int64_t M = check_rec(rec, K, torch::Device(torch::kCPU), "write_record_file");
+  ana::write_record_file(path, rec.data_ptr<int32_t>(), M, (int)K);
 }
 
 static py::object reader_acquire(ana::RecordReader& r) {
@@ -876,14 +820,11 @@ void emulate_allreduce(Tensor buf, int64_t channels, int64_t passes, double us) 
 
 void warm_rows(Tensor state, Tensor sink) {
   const auto dev = state.device();
-  check(state, "state", torch::kFloat32, dev);
+  const int64_t P = check_state(state, dev, "warm_rows");
   check(sink, "sink", torch::kInt32, dev);
-  TORCH_CHECK(state.dim() == 2 && state.size(1) == ana::kRowFloats, "state must be [P, 32]");
   TORCH_CHECK(sink.numel() >= 256, "sink needs 256 words");
   if (!dev.is_cuda()) return;  // nothing to warm on the host
-  check_hip(ana::launch_warm_rows(state.data_ptr<float>(), state.size(0),
-                                  reinterpret_cast<uint32_t*>(sink.data_ptr<int32_t>()), stream_of(state)),
-            "warm_rows");
+  check_hip(ana::launch_warm_rows(state.data_ptr<float>(), P, u32p(sink), stream_of(state)), "warm_rows");
 }
 
 // runtime/rerate.py window digest of the packed output rows (digest.hip); out [3 + 10K] fp64
@@ -892,7 +833,7 @@ void records_digest(Tensor rows, int64_t K, Tensor scratch, Tensor out, const c1
   check(rows, "rows", torch::kFloat32, dev);
   check(scratch, "scratch", torch::kFloat64, dev);
   check(out, "out", torch::kFloat64, dev);
-  TORCH_CHECK(K >= 1 && K <= 5, "records_digest: K in 1..5");
+  TORCH_CHECK(K >= 1 && K <= ana::kMaxTeamSize, "records_digest: K must be 1..5");
   TORCH_CHECK(rows.dim() == 2 && rows.size(1) >= 10 * K + 2 && rows.size(1) % 4 == 0 &&
                   256 % (rows.size(1) / 4) == 0,
               "records_digest: rows must be the packed [M, W] output rows (W / 4 a divisor of 256)");
@@ -932,7 +873,7 @@ Tensor records_select(Tensor rec, Tensor rows, int64_t base, int64_t P, Tensor b
   TORCH_CHECK(reinterpret_cast<uintptr_t>(rec.data_ptr()) % (K % 2 == 0 ? 8 : 16) == 0 &&
                   reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0,
               "records_select: rec and rows must be 16-B aligned");
-  const uint32_t* bm = reinterpret_cast<const uint32_t*>(bitmap.data_ptr<int32_t>());
+  const uint32_t* bm = u32p(bitmap);
   const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
   if (!dev.is_cuda()) {
     const int64_t n = ana::records_select_host((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1),
@@ -946,8 +887,7 @@ Tensor records_select(Tensor rec, Tensor rows, int64_t base, int64_t P, Tensor b
   Tensor counts = torch::empty({tiles}, i32);
   Tensor offsets = torch::empty({tiles + 1}, i32.dtype(torch::kInt64));
   check_hip(ana::launch_records_select_count((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M,
-                                             P, bm, reinterpret_cast<uint32_t*>(counts.data_ptr<int32_t>()),
-                                             offsets.data_ptr<int64_t>(), stream_of(rec)),
+                                             P, bm, u32p(counts), offsets.data_ptr<int64_t>(), stream_of(rec)),
             "records_select (count)");
   const int64_t n = offsets[tiles].item<int64_t>();  // the one synchronisation of a call
   TORCH_CHECK(n >= 0 && n <= M * 2 * K, "records_select: impossible hit count ", n);
@@ -966,12 +906,10 @@ Tensor records_select(Tensor rec, Tensor rows, int64_t base, int64_t P, Tensor b
 // once for all tracks and synchronises once, for the ranked counts that size the outputs.
 std::vector<Tensor> ladder(Tensor state, int64_t mask, int64_t score, double max_sigma) {
   const auto dev = state.device();
-  check(state, "state", torch::kFloat32, dev);
-  TORCH_CHECK(state.dim() == 2 && state.size(1) == ana::kRowFloats, "ladder: state must be [P, 32]");
+  const int64_t P = check_state(state, dev, "ladder");
   TORCH_CHECK(mask > 0 && (mask & ~(int64_t)ana::kLadderTrackMask) == 0,
               "ladder: the track mask must name some of tracks 0..6");
   TORCH_CHECK(score == ana::kLadderConservative || score == ana::kLadderMu, "ladder: unknown score ", score);
-  const int64_t P = state.size(0);
   TORCH_CHECK(P <= 0x7fffffffLL, "ladder: P must be below 2^31");
   const float bound = (float)max_sigma;
   const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
@@ -1006,23 +944,16 @@ std::vector<Tensor> ladder(Tensor state, int64_t mask, int64_t score, double max
   const int64_t stride = (P + 31) / 32 * 32;  // every track's keys start on a 128-B line
   Tensor keys = torch::empty({T, stride}, i32), ids = torch::empty({T, stride}, i32);
   Tensor counts = torch::empty({(int64_t)ana::kTracks}, i32);
-  auto u = [](Tensor& t) { return reinterpret_cast<uint32_t*>(t.data_ptr<int32_t>()); };
-  check_hip(ana::launch_ladder_keys(state.data_ptr<float>(), P, (uint32_t)mask, (int)score, bound, u(keys), u(ids),
-                                    stride, u(counts), s),
+  check_hip(ana::launch_ladder_keys(state.data_ptr<float>(), P, (uint32_t)mask, (int)score, bound, u32p(keys),
+                                    u32p(ids), stride, u32p(counts), s),
             "ladder_keys");
   const Tensor host_counts = counts.cpu();  // the one synchronisation of a build
-  // the sort's work buffers, shared by the tracks
-  Tensor kalt = torch::empty({P}, i32), valt = torch::empty({P}, i32);
-  Tensor ws = torch::empty({(int64_t)ana::radix_sort_workspace_bytes(P)}, i32.dtype(torch::kUInt8));
   for (int64_t j = 0; j < T; ++j) {
     const int64_t R = host_counts.data_ptr<int32_t>()[j];
     TORCH_CHECK(R >= 0 && R <= P, "ladder: impossible ranked count ", R);
-    uint32_t *k = u(keys) + j * stride, *v = u(ids) + j * stride;
-    int in_alt = 0;
-    check_hip(ana::launch_radix_sort_pairs(k, v, u(kalt), u(valt), P, 32, ws.data_ptr<uint8_t>(), &in_alt, s),
-              "ladder (sort)");
+    const auto sorted = sort_pairs_on_stream(keys[j].narrow(0, 0, P), ids[j].narrow(0, 0, P), P, 32, s);
     Tensor order = torch::empty({R}, i32), sc = torch::empty({R}, f32), rank = torch::empty({P}, i32);
-    check_hip(ana::launch_ladder_ranks(in_alt ? u(kalt) : k, in_alt ? u(valt) : v, P, R, order.data_ptr<int32_t>(),
+    check_hip(ana::launch_ladder_ranks(u32p(sorted[0]), u32p(sorted[1]), P, R, order.data_ptr<int32_t>(),
                                        sc.data_ptr<float>(), rank.data_ptr<int32_t>(), s),
               "ladder_ranks");
     out.push_back(order);
@@ -1036,29 +967,23 @@ std::vector<Tensor> ladder(Tensor state, int64_t mask, int64_t score, double max
 // attrs may be absent ("no attributes"); returns its pointer or null.
 const float* matchmake_roster(const Tensor& state, const c10::optional<Tensor>& attrs, const Tensor& vst,
                               const torch::Device& dev, const char* what) {
-  check(state, "state", torch::kFloat32, dev);
-  check(vst, "vst", torch::kFloat32, dev);
-  TORCH_CHECK(state.dim() == 2 && state.size(1) == ana::kRowFloats, what, ": state must be [P, 32]");
-  TORCH_CHECK(state.size(0) <= 0x7fffffffLL, what, ": P must be below 2^31");
-  TORCH_CHECK(vst.numel() == ana::kVstTiers, what, ": vst must have 31 entries (tiers -1..29)");
+  const int64_t P = check_state(state, dev, what);
+  check_vst(vst, dev, what);
+  TORCH_CHECK(P <= 0x7fffffffLL, what, ": P must be below 2^31");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(state.data_ptr()) % 16 == 0, what, ": state must be 16-B aligned");
   if (!attrs.has_value() || !attrs->defined()) return nullptr;
-  check(*attrs, "attrs", torch::kFloat32, dev);
-  TORCH_CHECK(attrs->dim() == 2 && attrs->size(0) == state.size(0) && attrs->size(1) == 4, what,
-              ": attrs must be [P, 4]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(attrs->data_ptr()) % 16 == 0, what, ": attrs must be 16-B aligned");
-  return attrs->data_ptr<float>();
+  const float* at = check_attrs(*attrs, P, dev, what);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(at) % 16 == 0, what, ": attrs must be 16-B aligned");
+  return at;
 }
 
 // packed rows [M, 4] int32: status, quality bits, p_win0 bits, 0 (ops/matchmake.py views them)
 Tensor preview(Tensor rec, int64_t K, Tensor state, c10::optional<Tensor> attrs, Tensor vst, double beta2,
                double unknown_sigma) {
   const auto dev = rec.device();
-  check(rec, "rec", torch::kInt32, dev);
-  TORCH_CHECK(K >= 1 && K <= ana::kSplitMaxK, "preview: K must be 1..5");
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == 2 * K + 2, "preview: rec must be [M, 2K+2]");
+  const int64_t M = check_rec(rec, K, dev, "preview");
   const float* at = matchmake_roster(state, attrs, vst, dev, "preview");
-  const int64_t M = rec.size(0), P = state.size(0);
+  const int64_t P = state.size(0);
   Tensor out = torch::empty({M, (int64_t)ana::kPreviewWords}, rec.options());
   if (M == 0) return out;
   if (dev.is_cuda()) {
@@ -1080,7 +1005,7 @@ std::vector<Tensor> balance(Tensor lobbies, int64_t K, Tensor state, c10::option
                             int64_t mode, double beta2, double unknown_sigma) {
   const auto dev = lobbies.device();
   check(lobbies, "lobbies", torch::kInt32, dev);
-  TORCH_CHECK(K >= 1 && K <= ana::kSplitMaxK, "balance: K must be 1..5");
+  TORCH_CHECK(K >= 1 && K <= ana::kMaxTeamSize, "balance: K must be 1..5");
   TORCH_CHECK(lobbies.dim() == 2 && lobbies.size(1) == 2 * K, "balance: lobbies must be [L, 2K]");
   TORCH_CHECK(mode >= 0 && mode < ana::kModes, "balance: mode must be 0..5");
   const float* at = matchmake_roster(state, attrs, vst, dev, "balance");
@@ -1114,66 +1039,46 @@ std::vector<Tensor> queue_order(Tensor queue, Tensor state, c10::optional<Tensor
   const int64_t Q = queue.size(0), P = state.size(0);
   Tensor keys = torch::empty({Q}, queue.options()), vals = torch::empty({Q}, queue.options());
   if (Q == 0) return {keys, vals};
-  auto u = [](Tensor& t) { return reinterpret_cast<uint32_t*>(t.data_ptr<int32_t>()); };
   if (!dev.is_cuda()) {
     TORCH_CHECK(ana::host_queue_keys(queue.data_ptr<int32_t>(), Q, state.data_ptr<float>(), at,
-                                     vst.data_ptr<float>(), P, (int)mode, (float)unknown_sigma, u(keys),
-                                     u(vals)) == 0, "queue_order: bad arguments");
+                                     vst.data_ptr<float>(), P, (int)mode, (float)unknown_sigma, u32p(keys),
+                                     u32p(vals)) == 0, "queue_order: bad arguments");
     Tensor sk = torch::empty({Q}, queue.options()), sv = torch::empty({Q}, queue.options());
-    const uint32_t* k = u(keys);
-    uint32_t* order = u(sv);
+    const uint32_t* k = u32p(keys);
+    uint32_t* order = u32p(sv);
     std::iota(order, order + Q, 0u);
     std::stable_sort(order, order + Q, [&](uint32_t a, uint32_t b) { return k[a] < k[b]; });
-    for (int64_t i = 0; i < Q; ++i) u(sk)[i] = k[order[i]];
+    for (int64_t i = 0; i < Q; ++i) u32p(sk)[i] = k[order[i]];
     return {sk, sv};
   }
   const hipStream_t s = stream_of(queue);
   check_hip(ana::launch_queue_keys(queue.data_ptr<int32_t>(), Q, state.data_ptr<float>(), at, vst.data_ptr<float>(),
-                                   P, (int)mode, (float)unknown_sigma, u(keys), u(vals), s),
+                                   P, (int)mode, (float)unknown_sigma, u32p(keys), u32p(vals), s),
             "queue_keys");
-  Tensor kalt = torch::empty({Q}, queue.options()), valt = torch::empty({Q}, queue.options());
-  Tensor ws = torch::empty({(int64_t)ana::radix_sort_workspace_bytes(Q)}, queue.options().dtype(torch::kUInt8));
-  int in_alt = 0;
-  check_hip(ana::launch_radix_sort_pairs(u(keys), u(vals), u(kalt), u(valt), Q, 32, ws.data_ptr<uint8_t>(), &in_alt, s),
-            "queue_order (sort)");
-  if (in_alt) return {kalt, valt};
-  return {keys, vals};
+  return sort_pairs_on_stream(keys, vals, Q, 32, s);
 }
 
 // (lanes of a lane group, lobbies per wave, lobbies per workgroup) of preview / balance at team size K
 std::tuple<int64_t, int64_t, int64_t> matchmake_geometry(int64_t K) {
-  TORCH_CHECK(K >= 1 && K <= ana::kSplitMaxK, "K must be 1..5");
+  TORCH_CHECK(K >= 1 && K <= ana::kMaxTeamSize, "matchmake_geometry: K must be 1..5");
   const int G = ana::split_group_lanes((int)K);
   return {G, 64 / G, ana::kMatchmakeThreads / G};
 }
 
 std::vector<int64_t> split_masks(int64_t K) {
+  TORCH_CHECK(K >= 1 && K <= ana::kMaxTeamSize, "split_masks: K must be 1..5");
   std::vector<int64_t> out;
-  auto fill = [&](const auto& t) {
-    for (uint16_t m : t.mask) out.push_back(m);
-  };
-  switch (K) {
-    case 1: fill(ana::kSplits<1>); break;
-    case 2: fill(ana::kSplits<2>); break;
-    case 3: fill(ana::kSplits<3>); break;
-    case 4: fill(ana::kSplits<4>); break;
-    case 5: fill(ana::kSplits<5>); break;
-    default: TORCH_CHECK(false, "K must be 1..5");
-  }
+  ana::with_team_size((int)K, [&](auto k) {
+    for (uint16_t m : ana::kSplits<decltype(k)::value>.mask) out.push_back(m);
+  });
   return out;
 }
 
 void reset_tags(Tensor state) {
   const auto dev = state.device();
-  check(state, "state", torch::kFloat32, dev);
-  TORCH_CHECK(state.dim() == 2 && state.size(1) == ana::kRowFloats, "state must be [P, 32]");
-  if (dev.is_cuda()) {
-    check_hip(ana::launch_reset_tags(state.data_ptr<float>(), state.size(0), stream_of(state)),
-              "reset_tags");
-  } else {
-    float* p = state.data_ptr<float>();
-    for (int64_t i = 0; i < state.numel(); i += 2) p[i + 1] = 0.f;
-  }
+  const int64_t P = check_state(state, dev, "reset_tags");
+  if (dev.is_cuda()) check_hip(ana::launch_reset_tags(state.data_ptr<float>(), P, stream_of(state)), "reset_tags");
+  else ana::host_reset_tags(state.data_ptr<float>(), P);
 }
 
 }  // namespace

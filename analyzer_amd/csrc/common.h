@@ -19,6 +19,8 @@
 
 #include <stdint.h>
 
+#include <type_traits>
+
 // 1 in the diagnostic library (python -m analyzer_amd.build_ext --diag): kernel
 // variants that exist only to take a kernel apart (telemetry.hip)
 #ifndef ANA_DIAG_BUILD
@@ -54,6 +56,7 @@ constexpr int64_t kMaxSlots = 1ll << kSlotBits;
 constexpr int kModes = 6;
 constexpr int kModeUnsupported = 255;
 constexpr int kVstTiers = 31;     // tiers -1..29
+constexpr int kMaxTeamSize = 5;   // K: players per roster; every K-templated kernel exists for 1..5
 
 // per-match status codes (the reference's outcomes and error classes)
 enum Status : uint8_t {
@@ -168,6 +171,23 @@ ANA_HD uint8_t early_status_k(const int32_t* r, int S, int64_t P) {
     default: return kErrBadRecord;
   }
 }
+
+// Host side: a runtime team size as a template argument.  Calls
+// f(std::integral_constant<int, K>{}) for K in 1..kMaxTeamSize and returns true;
+// returns false without calling f otherwise (launchers: hipErrorInvalidValue, host
+// mirrors: their error value, bindings: TORCH_CHECK).
+template <class F>
+inline bool with_team_size(int K, F&& f) {
+  switch (K) {
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    case 3: f(std::integral_constant<int, 3>{}); return true;
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    case 5: f(std::integral_constant<int, 5>{}); return true;
+    default: return false;
+  }
+}
+static_assert(kMaxTeamSize == 5, "with_team_size and early_status_k list the team sizes");
 
 // ---------------------------------------------------------------- RNG (K7)
 // Counter-based: every random number is a pure function of (seed, index,

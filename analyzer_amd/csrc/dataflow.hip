@@ -1007,6 +1007,9 @@ __global__ void __launch_bounds__(64) zero_ctrl2_kernel(uint32_t* __restrict__ a
   if ((int)threadIdx.x < nb) b[threadIdx.x] = 0u;
 }
 
+template <int V>
+using Int = std::integral_constant<int, V>;
+
 int launch_rate(int K, const int32_t* rec, const uint32_t* link, int32_t* deps, float* state,
                 const float* attrs, float* first_prior, const RateOut& out, uint32_t* ctrl,
                 const RateParams& prm, const TelemetryParams& tp, int blocks, hipStream_t s) {
@@ -1039,42 +1042,36 @@ int launch_rate(int K, const int32_t* rec, const uint32_t* link, int32_t* deps, 
   // config 3 step 21.5 vs 21.9 ms, profiles/r2/tight_groups.log) -> auto = tight
   // for 5v5 only.
   const bool tight = prm.tight_groups > 0 || (prm.tight_groups < 0 && K == 5);
-#define ANA_RATE_LAUNCH_W(k, g, tele, diag, w)                                                     \
-  hipLaunchKernelGGL((rate_dataflow_kernel<k, g, tele, diag, w>), dim3((unsigned)blocks), dim3(256), 0, s, \
-                     rec, link, deps, state, attrs, first_prior, out.s_mu, out.row, ctrl, prm, tp)
-#define ANA_RATE_LAUNCH_D(k, g, tele, diag)                                                        \
-  do {                                                                                             \
-    if constexpr (tele == 0 && !diag && k <= 3 && (g & (g - 1)) == 0) {                            \
-      if (blocks > 256) ANA_RATE_LAUNCH_W(k, g, tele, diag, 4); /* two waves per SIMD */          \
-      else ANA_RATE_LAUNCH_W(k, g, tele, diag, 1);                                                 \
-    } else {                                                                                       \
-      ANA_RATE_LAUNCH_W(k, g, tele, diag, 1);                                                      \
-    }                                                                                              \
-  } while (0)
-#define ANA_RATE_LAUNCH(k, g)                                      \
-  do {                                                             \
-    if (tp.evoff && tp.role_stride < 0) ANA_RATE_LAUNCH_D(k, g, 2, false); \
-    else if (tp.evoff) ANA_RATE_LAUNCH_D(k, g, 1, false);          \
-    else if (prm.diag) ANA_RATE_LAUNCH_D(k, g, 0, true);           \
-    else ANA_RATE_LAUNCH_D(k, g, 0, false);                        \
-  } while (0)
-  switch (K) {
-    case 1: ANA_RATE_LAUNCH(1, 2); break;
-    case 2: ANA_RATE_LAUNCH(2, 4); break;
-    case 3:
-      if (tight) ANA_RATE_LAUNCH(3, 6);
-      else ANA_RATE_LAUNCH(3, 8);
-      break;
-    case 4: ANA_RATE_LAUNCH(4, 8); break;
-    case 5:
-      if (tight) ANA_RATE_LAUNCH(5, 10);
-      else ANA_RATE_LAUNCH(5, 16);
-      break;
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef ANA_RATE_LAUNCH
-#undef ANA_RATE_LAUNCH_D
-  return (int)hipGetLastError();
+  // the instantiation <K, G, TELE, DIAG, WPE> of a launch, chosen in three steps
+  auto launch_w = [&](auto k, auto g, auto tele, auto diag, auto w) {
+    hipLaunchKernelGGL((rate_dataflow_kernel<decltype(k)::value, decltype(g)::value, decltype(tele)::value,
+                                             decltype(diag)::value, decltype(w)::value>),
+                       dim3((unsigned)blocks), dim3(256), 0, s, rec, link, deps, state, attrs, first_prior, out.s_mu,
+                       out.row, ctrl, prm, tp);
+  };
+  auto launch_d = [&](auto k, auto g, auto tele, auto diag) {
+    constexpr int kK = decltype(k)::value, kG = decltype(g)::value;
+    if constexpr (decltype(tele)::value == 0 && !decltype(diag)::value && kK <= 3 && (kG & (kG - 1)) == 0) {
+      if (blocks > 256) launch_w(k, g, tele, diag, Int<4>{});  // two waves per SIMD
+      else launch_w(k, g, tele, diag, Int<1>{});
+    } else {
+      launch_w(k, g, tele, diag, Int<1>{});
+    }
+  };
+  auto launch = [&](auto k, auto g) {
+    if (tp.evoff && tp.role_stride < 0) launch_d(k, g, Int<2>{}, std::false_type{});
+    else if (tp.evoff) launch_d(k, g, Int<1>{}, std::false_type{});
+    else if (prm.diag) launch_d(k, g, Int<0>{}, std::true_type{});
+    else launch_d(k, g, Int<0>{}, std::false_type{});
+  };
+  const bool known = with_team_size(K, [&](auto k) {
+    constexpr int kK = decltype(k)::value;
+    if constexpr (kK == 3 || kK == 5) {  // 2K is a power of two otherwise
+      if (tight) return launch(k, Int<2 * kK>{});
+    }
+    launch(k, Int<(kK == 1 ? 2 : kK == 2 ? 4 : kK <= 4 ? 8 : 16)>{});
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 }  // namespace ana

@@ -164,19 +164,14 @@ size_t records_digest_scratch_doubles(int K) { return (size_t)kDigestBlocks * (3
 
 int launch_records_digest(int K, const float* rows, int64_t M, int64_t W, double* scratch, double* out,
                           int64_t* hist, hipStream_t s) {
-  if (K < 1 || K > 5 || W < 5 * 2 * K + 2 || (W & 3)) return (int)hipErrorInvalidValue;
+  if (K < 1 || K > kMaxTeamSize || W < 5 * 2 * K + 2 || (W & 3)) return (int)hipErrorInvalidValue;
   const int Q = (int)(W / 4);
   if (Q > kDigestThreads || kDigestThreads % Q != 0) return (int)hipErrorInvalidValue;
   const int D = 3 + 10 * K;
-  switch (K) {
-#define ANA_DIGEST_CASE(k)                                                                                      \
-  case k:                                                                                                       \
-    hipLaunchKernelGGL(records_digest_kernel<k>, dim3(kDigestBlocks), dim3(kDigestThreads), 0, s, rows, M, Q,  \
-                       scratch, reinterpret_cast<unsigned long long*>(hist));                                   \
-    break;
-    ANA_DIGEST_CASE(1) ANA_DIGEST_CASE(2) ANA_DIGEST_CASE(3) ANA_DIGEST_CASE(4) ANA_DIGEST_CASE(5)
-#undef ANA_DIGEST_CASE
-  }
+  with_team_size(K, [&](auto k) {
+    hipLaunchKernelGGL(records_digest_kernel<decltype(k)::value>, dim3(kDigestBlocks), dim3(kDigestThreads), 0, s, rows,
+                       M, Q, scratch, reinterpret_cast<unsigned long long*>(hist));
+  });
   hipLaunchKernelGGL(digest_finish_kernel, dim3(D), dim3(kDigestThreads), 0, s, scratch, D, kDigestBlocks, out);
   return (int)hipGetLastError();
 }

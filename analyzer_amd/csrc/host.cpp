@@ -2,7 +2,8 @@
 // kernels, run sequentially in stream order.  It is the exact-semantics oracle
 // for the device dataflow executor (fp64 by default) and the CPU path for the
 // plumbing configuration (BASELINE config 1).  It is not a fallback for GPU
-// tensors: device tensors always go to the HIP kernels.
+// tensors: device tensors always go to the HIP kernels.  Every mirror takes raw
+// pointers, so the sanitized stand-alone self-test (tests/native) reaches all of them.
 #include "host.h"
 
 #include <math.h>
@@ -29,14 +30,7 @@ static void gen_stream_k(const GenStreamParams& g, int32_t* rec, int64_t M) {
 }
 
 int host_gen_stream(int K, const GenStreamParams& g, int32_t* rec, int64_t M) {
-  switch (K) {
-    case 1: gen_stream_k<1>(g, rec, M); return 0;
-    case 2: gen_stream_k<2>(g, rec, M); return 0;
-    case 3: gen_stream_k<3>(g, rec, M); return 0;
-    case 4: gen_stream_k<4>(g, rec, M); return 0;
-    case 5: gen_stream_k<5>(g, rec, M); return 0;
-    default: return -1;
-  }
+  return with_team_size(K, [&](auto k) { gen_stream_k<decltype(k)::value>(g, rec, M); }) ? 0 : -1;
 }
 
 // Same outputs as the device schedule (common.h kLinkWords): link[slot] =
@@ -72,7 +66,7 @@ void host_gen_event_counts(const GenEventParams& g, int64_t base, int64_t M, int
 
 int host_gen_events(int K, const GenEventParams& g, int64_t base, const int32_t* rec,
                     const int64_t* evoff, int64_t M, int32_t* events) {
-  if (K < 1 || K > 5) return -1;
+  if (K < 1 || K > kMaxTeamSize) return -1;
   const int S = 2 * K;
   for (int64_t m = 0; m < M; ++m) {
     const uint32_t m0 = (uint32_t)rec[m * (S + 2) + S];
@@ -133,25 +127,13 @@ static int64_t levels_k(const int32_t* rec, int64_t M, int64_t P, int32_t* level
 }
 
 int64_t host_levels(int K, const int32_t* rec, int64_t M, int64_t P, int32_t* level) {
-  switch (K) {
-    case 1: return levels_k<1>(rec, M, P, level);
-    case 2: return levels_k<2>(rec, M, P, level);
-    case 3: return levels_k<3>(rec, M, P, level);
-    case 4: return levels_k<4>(rec, M, P, level);
-    case 5: return levels_k<5>(rec, M, P, level);
-    default: return -1;
-  }
+  int64_t depth = -1;
+  with_team_size(K, [&](auto k) { depth = levels_k<decltype(k)::value>(rec, M, P, level); });
+  return depth;
 }
 
 int host_schedule(int K, const int32_t* rec, int64_t M, int64_t P, uint32_t* link, int32_t* deps) {
-  switch (K) {
-    case 1: schedule_k<1>(rec, M, P, link, deps); return 0;
-    case 2: schedule_k<2>(rec, M, P, link, deps); return 0;
-    case 3: schedule_k<3>(rec, M, P, link, deps); return 0;
-    case 4: schedule_k<4>(rec, M, P, link, deps); return 0;
-    case 5: schedule_k<5>(rec, M, P, link, deps); return 0;
-    default: return -1;
-  }
+  return with_team_size(K, [&](auto k) { schedule_k<decltype(k)::value>(rec, M, P, link, deps); }) ? 0 : -1;
 }
 
 template <typename T, int K>
@@ -218,14 +200,9 @@ static void rate_k(const int32_t* rec, float* state, const float* attrs, float* 
 template <typename T>
 static int rate_t(int K, const int32_t* rec, float* state, const float* attrs, float* first_prior,
                   const RateOut& out, const RateParams& prm) {
-  switch (K) {
-    case 1: rate_k<T, 1>(rec, state, attrs, first_prior, out, prm); return 0;
-    case 2: rate_k<T, 2>(rec, state, attrs, first_prior, out, prm); return 0;
-    case 3: rate_k<T, 3>(rec, state, attrs, first_prior, out, prm); return 0;
-    case 4: rate_k<T, 4>(rec, state, attrs, first_prior, out, prm); return 0;
-    case 5: rate_k<T, 5>(rec, state, attrs, first_prior, out, prm); return 0;
-    default: return -1;
-  }
+  const bool known =
+      with_team_size(K, [&](auto k) { rate_k<T, decltype(k)::value>(rec, state, attrs, first_prior, out, prm); });
+  return known ? 0 : -1;
 }
 
 int host_rate(int K, bool fp64, const int32_t* rec, float* state, const float* attrs,
@@ -285,6 +262,69 @@ void host_prefix_delta(const float* s0, const float* prefix, const float* attrs,
     prefix_delta_player(s0 + p * kBaseFloats, prefix + p * 14, attrs + p * 4, vst, unknown_sigma, delta + p * 16);
 }
 
+// C2 exchange (sweep.hip pack_rows / unpack_rows / check_round): entries of 33 words, the
+// roster row of a rated match's slot and its player id (-1: no row)
+int host_pack_rows(const int32_t* rec, int K, int64_t m, const uint8_t* status, int64_t sstride, const float* state,
+                   int64_t P, float* out, int64_t cap) {
+  if (K < 1 || K > kMaxTeamSize) return -1;
+  const int S = 2 * K;
+  for (int64_t e = 0; e < cap; ++e) {
+    int32_t id = -1;
+    if (e < m * S) {
+      const int64_t i = e / S;
+      const int j = (int)(e % S);
+      const uint32_t m0 = (uint32_t)rec[i * (S + 2) + S];
+      const int n = j < K ? meta_n0(m0) : meta_n1(m0);
+      const int32_t v = rec[i * (S + 2) + j];
+      if (status[i * sstride] == kRated && (j < K ? j : j - K) < n && v >= 0 && v < P) id = v;
+    }
+    float* o = out + e * 33;
+    if (id >= 0) memcpy(o, state + (int64_t)id * kRowFloats, kRowFloats * sizeof(float));
+    memcpy(o + kRowFloats, &id, 4);
+  }
+  return 0;
+}
+
+// rows of the entries with an id in 0..P-1 into the roster, tags zeroed
+void host_unpack_rows(const float* buf, int64_t n, float* state, int64_t P) {
+  for (int64_t e = 0; e < n; ++e) {
+    const float* b = buf + e * 33;
+    int32_t id;
+    memcpy(&id, b + kRowFloats, 4);
+    if (id < 0 || id >= P) continue;
+    for (int k = 0; k < kRowFloats; ++k) state[(int64_t)id * kRowFloats + k] = (k & 1) ? 0.f : b[k];
+  }
+}
+
+// owner[p] = (round + 1) << 32 | (match + 1) of the first match of the round that holds p
+int host_check_round(const int32_t* rec, int K, const int64_t* idx, int64_t m, int64_t P, uint32_t round,
+                     uint64_t* owner, int32_t* flag) {
+  if (K < 1 || K > kMaxTeamSize) return -1;
+  const int S = 2 * K;
+  const uint64_t tag = (uint64_t)round + 1;
+  for (int64_t i = 0; i < m; ++i) {
+    const int32_t* r = rec + idx[i] * (S + 2);
+    if (early_status_k(r, S, P) != kRated) continue;
+    const uint32_t m0 = (uint32_t)r[S];
+    const uint64_t mine = (tag << 32) | (uint64_t)(idx[i] + 1);
+    for (int j = 0; j < S; ++j) {
+      const int n = j < K ? meta_n0(m0) : meta_n1(m0);
+      const int32_t p = r[j];
+      if ((j < K ? j : j - K) >= n || p < 0 || p >= P) continue;
+      if (owner[p] >> 32 == tag) {
+        if (owner[p] != mine) flag[0] |= 1;
+      } else {
+        owner[p] = mine;
+      }
+    }
+  }
+  return 0;
+}
+
+void host_reset_tags(float* state, int64_t P) {
+  for (int64_t i = 0; i < P * kRowFloats; i += 2) state[i + 1] = 0.f;
+}
+
 // K10: the device's three launches as one sequential walk (the order is the walk's)
 template <int K>
 static int64_t records_select_k(const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base, int64_t P,
@@ -310,14 +350,9 @@ static int64_t records_select_k(const int32_t* rec, const float* rows, int64_t W
 
 int64_t records_select_host(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base,
                             int64_t P, const uint32_t* bitmap, int32_t* hits) {
-  switch (K) {
-    case 1: return records_select_k<1>(rec, rows, W, M, base, P, bitmap, hits);
-    case 2: return records_select_k<2>(rec, rows, W, M, base, P, bitmap, hits);
-    case 3: return records_select_k<3>(rec, rows, W, M, base, P, bitmap, hits);
-    case 4: return records_select_k<4>(rec, rows, W, M, base, P, bitmap, hits);
-    case 5: return records_select_k<5>(rec, rows, W, M, base, P, bitmap, hits);
-    default: return -1;
-  }
+  int64_t n = -1;
+  with_team_size(K, [&](auto k) { n = records_select_k<decltype(k)::value>(rec, rows, W, M, base, P, bitmap, hits); });
+  return n;
 }
 
 // K11: the device's three stages on one track -- keys in id order, a stable sort of the
@@ -404,14 +439,9 @@ static void preview_k(const int32_t* rec, int64_t M, const float* state, const f
 int host_preview(int K, const int32_t* rec, int64_t M, const float* state, const float* attrs, const float* vst,
                  int64_t P, float beta2, float unknown_sigma, int32_t* out) {
   if (M < 0 || P < 0 || P > 0x7fffffffll) return -1;
-  switch (K) {
-    case 1: preview_k<1>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); return 0;
-    case 2: preview_k<2>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); return 0;
-    case 3: preview_k<3>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); return 0;
-    case 4: preview_k<4>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); return 0;
-    case 5: preview_k<5>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); return 0;
-    default: return -1;
-  }
+  const bool known = with_team_size(
+      K, [&](auto k) { preview_k<decltype(k)::value>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); });
+  return known ? 0 : -1;
 }
 
 // fp32 player_prior of one player, as the device's load_prior
@@ -501,14 +531,10 @@ static void balance_k(const int32_t* lobbies, int64_t L, const float* state, con
 int host_balance(int K, const int32_t* lobbies, int64_t L, const float* state, const float* attrs, const float* vst,
                  int64_t P, int mode, float beta2, float unknown_sigma, int32_t* out, int32_t* records) {
   if (L < 0 || P < 0 || P > 0x7fffffffll || mode < 0 || mode >= kModes) return -1;
-  switch (K) {
-    case 1: balance_k<1>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records); return 0;
-    case 2: balance_k<2>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records); return 0;
-    case 3: balance_k<3>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records); return 0;
-    case 4: balance_k<4>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records); return 0;
-    case 5: balance_k<5>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records); return 0;
-    default: return -1;
-  }
+  const bool known = with_team_size(K, [&](auto k) {
+    balance_k<decltype(k)::value>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records);
+  });
+  return known ? 0 : -1;
 }
 
 int host_queue_keys(const int32_t* queue, int64_t Q, const float* state, const float* attrs, const float* vst,

@@ -40,6 +40,16 @@ void host_correct_records(int K, const int32_t* rec, int64_t M, float* rows, int
                           int64_t P);
 void host_prefix_delta(const float* s0, const float* prefix, const float* attrs, const float* vst,
                        float unknown_sigma, float* delta, int64_t P);
+// C2 exchange host mirrors (kernels.h launch_pack_rows / launch_unpack_rows / launch_check_round):
+// out / buf are [cap][33] entries = a roster row + the player id (-1: none); state is [P][32].
+// pack and check_round return -1 for a K out of range.
+int host_pack_rows(const int32_t* rec, int K, int64_t m, const uint8_t* status, int64_t sstride, const float* state,
+                   int64_t P, float* out, int64_t cap);
+void host_unpack_rows(const float* buf, int64_t n, float* state, int64_t P);
+int host_check_round(const int32_t* rec, int K, const int64_t* idx, int64_t m, int64_t P, uint32_t round,
+                     uint64_t* owner, int32_t* flag);
+// zero the dataflow tags of state [P][32]
+void host_reset_tags(float* state, int64_t P);
 // K10 host mirror (select_core.h): the hits of the bitmap's players in rec [M][2K+2] joined
 // with rows [M][W], ascending (match, slot), bit-identical to the device.  Returns their
 // number (-1: K out of range); hits == nullptr only counts.

@@ -68,14 +68,10 @@ int launch_gen_roster(const GenRosterParams& g, float* state, float* attrs, hipS
 int launch_gen_stream(int K, const GenStreamParams& g, int32_t* rec, int64_t M, hipStream_t s) {
   if (M <= 0) return 0;
   const unsigned blocks = (unsigned)((M + 255) / 256);
-  switch (K) {
-#define ANA_GEN_CASE(k) \
-  case k: hipLaunchKernelGGL(gen_stream_kernel<k>, dim3(blocks), dim3(256), 0, s, g, rec, M); break;
-    ANA_GEN_CASE(1) ANA_GEN_CASE(2) ANA_GEN_CASE(3) ANA_GEN_CASE(4) ANA_GEN_CASE(5)
-#undef ANA_GEN_CASE
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+  const bool known = with_team_size(K, [&](auto k) {
+    hipLaunchKernelGGL(gen_stream_kernel<decltype(k)::value>, dim3(blocks), dim3(256), 0, s, g, rec, M);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // Zero every tag of the roster (after an epoch wrap, or for a roster of unknown origin).
@@ -363,30 +359,27 @@ int launch_schedule(int K, const int32_t* rec, int64_t M, int64_t P, uint32_t* l
   // zero_ctrl: also zero the executor's control words (overflow = ctrl[0], ctrl[1..15]) for
   // a rate launch that follows on this stream and then skips its own zeroing dispatch
   const int nz = zero_ctrl ? 16 : 1;
+  if (K < 1 || K > kMaxTeamSize) return (int)hipErrorInvalidValue;
   const int64_t n = M * 2 * K;
-  if (n > 0 && n <= kSmallSched && P < 0x7fffffffLL && K >= 1 && K <= 5) {
+  if (n > 0 && n <= kSmallSched && P < 0x7fffffffLL) {
     const int e = n <= 2048 ? 2 : n <= 4096 ? 4 : 8;  // elements per thread
     const char* small_e = getenv("ANA_SCHED_SMALL");  // per schedule (A/B in one process)
     const bool bitonic = small_e && small_e[0] == 'b';
-    switch (K) {
-#define ANA_SMALL_CASE(k)                                                                            \
-  case k:                                                                                            \
-    if (!bitonic)                                                                                    \
-      hipLaunchKernelGGL((sched_hash_kernel<k>), dim3(1), dim3(kSmallThreads), 0, s, rec, M,         \
-                         (uint32_t)P, link, deps, overflow, nz, epoch_bump);                         \
-    else if (e == 2)                                                                                      \
-      hipLaunchKernelGGL((sched_small_kernel<k, 2>), dim3(1), dim3(kSmallThreads), 0, s, rec, M,     \
-                         (uint32_t)P, link, deps, overflow);                                         \
-    else if (e == 4)                                                                                 \
-      hipLaunchKernelGGL((sched_small_kernel<k, 4>), dim3(1), dim3(kSmallThreads), 0, s, rec, M,     \
-                         (uint32_t)P, link, deps, overflow);                                         \
-    else                                                                                             \
-      hipLaunchKernelGGL((sched_small_kernel<k, 8>), dim3(1), dim3(kSmallThreads), 0, s, rec, M,     \
-                         (uint32_t)P, link, deps, overflow);                                         \
-    break;
-      ANA_SMALL_CASE(1) ANA_SMALL_CASE(2) ANA_SMALL_CASE(3) ANA_SMALL_CASE(4) ANA_SMALL_CASE(5)
-#undef ANA_SMALL_CASE
-    }
+    with_team_size(K, [&](auto k) {
+      constexpr int kK = decltype(k)::value;
+      if (!bitonic)
+        hipLaunchKernelGGL((sched_hash_kernel<kK>), dim3(1), dim3(kSmallThreads), 0, s, rec, M, (uint32_t)P, link,
+                           deps, overflow, nz, epoch_bump);
+      else if (e == 2)
+        hipLaunchKernelGGL((sched_small_kernel<kK, 2>), dim3(1), dim3(kSmallThreads), 0, s, rec, M, (uint32_t)P,
+                           link, deps, overflow);
+      else if (e == 4)
+        hipLaunchKernelGGL((sched_small_kernel<kK, 4>), dim3(1), dim3(kSmallThreads), 0, s, rec, M, (uint32_t)P,
+                           link, deps, overflow);
+      else
+        hipLaunchKernelGGL((sched_small_kernel<kK, 8>), dim3(1), dim3(kSmallThreads), 0, s, rec, M, (uint32_t)P,
+                           link, deps, overflow);
+    });
     if (bitonic && zero_ctrl) ANA_HIP_CHECK(hipMemsetAsync(overflow, 0, 64, s));
     if (bitonic && epoch_bump) hipLaunchKernelGGL(epoch_bump_kernel, dim3(1), dim3(1), 0, s, epoch_bump);
     return (int)hipGetLastError();
@@ -396,7 +389,7 @@ int launch_schedule(int K, const int32_t* rec, int64_t M, int64_t P, uint32_t* l
     if (epoch_bump) hipLaunchKernelGGL(epoch_bump_kernel, dim3(1), dim3(1), 0, s, epoch_bump);
     return 0;
   }
-  if (n > kMaxSlots || P >= 0x7fffffffLL || K < 1 || K > 5) return (int)hipErrorInvalidValue;
+  if (n > kMaxSlots || P >= 0x7fffffffLL) return (int)hipErrorInvalidValue;
   if (ws_bytes < schedule_workspace_bytes(n, P)) return (int)hipErrorInvalidValue;
   // the counters, the control words and the epoch bump are the first sort kernel's
   // side duties (radix_sort.hip SchedInit): no fill dispatches in front of the sort

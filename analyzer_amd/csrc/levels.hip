@@ -218,14 +218,10 @@ int launch_levels(int K, const int32_t* rec, const uint32_t* link, int32_t* deps
   const int64_t chunks = (M + 63) / 64;
   const int64_t waves = chunks < (int64_t)kLvlBlocks * 4 ? chunks : (int64_t)kLvlBlocks * 4;
   const dim3 grid((unsigned)((waves + 3) / 4)), block(kLvlThreads);
-  switch (K) {
-#define ANA_LVL_CASE(k) \
-  case k: hipLaunchKernelGGL((levels_kernel<k>), grid, block, 0, s, rec, link, deps, pushed, level, M, P, ctrl); break;
-    ANA_LVL_CASE(1) ANA_LVL_CASE(2) ANA_LVL_CASE(3) ANA_LVL_CASE(4) ANA_LVL_CASE(5)
-#undef ANA_LVL_CASE
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+  const bool known = with_team_size(K, [&](auto k) {
+    hipLaunchKernelGGL((levels_kernel<decltype(k)::value>), grid, block, 0, s, rec, link, deps, pushed, level, M, P, ctrl);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 }  // namespace ana

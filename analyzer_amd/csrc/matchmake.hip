@@ -299,13 +299,11 @@ int launch_preview(int K, const int32_t* rec, int64_t M, const float* state, con
   if (K < 1 || K > kSplitMaxK || M < 0 || bad_roster_args(state, attrs, vst, P) || (M > 0 && (!rec || !out)))
     return (int)hipErrorInvalidValue;
   if (M == 0) return 0;
-  switch (K) {
-    case 1: return preview_k<1>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out, s);
-    case 2: return preview_k<2>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out, s);
-    case 3: return preview_k<3>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out, s);
-    case 4: return preview_k<4>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out, s);
-    default: return preview_k<5>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out, s);
-  }
+  int rc = (int)hipErrorInvalidValue;
+  with_team_size(K, [&](auto k) {
+    rc = preview_k<decltype(k)::value>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out, s);
+  });
+  return rc;
 }
 
 int launch_balance(int K, const int32_t* lobbies, int64_t L, const float* state, const float* attrs,
@@ -315,13 +313,11 @@ int launch_balance(int K, const int32_t* lobbies, int64_t L, const float* state,
       (L > 0 && (!lobbies || !out || !records)))
     return (int)hipErrorInvalidValue;
   if (L == 0) return 0;
-  switch (K) {
-    case 1: return balance_k<1>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records, s);
-    case 2: return balance_k<2>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records, s);
-    case 3: return balance_k<3>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records, s);
-    case 4: return balance_k<4>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records, s);
-    default: return balance_k<5>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records, s);
-  }
+  int rc = (int)hipErrorInvalidValue;
+  with_team_size(K, [&](auto k) {
+    rc = balance_k<decltype(k)::value>(lobbies, L, state, attrs, vst, P, mode, beta2, unknown_sigma, out, records, s);
+  });
+  return rc;
 }
 
 int launch_queue_keys(const int32_t* queue, int64_t Q, const float* state, const float* attrs, const float* vst,

@@ -27,7 +27,7 @@
 
 namespace ana {
 
-constexpr int kSplitMaxK = 5;
+constexpr int kSplitMaxK = kMaxTeamSize;
 constexpr int kPreviewWords = 4;  // packed preview row: status, quality, p_win0, 0
 constexpr int kBalanceWords = 8;  // packed balance row: status, split, team0, quality, p_win0, quality_given, 0, 0
 

@@ -647,19 +647,14 @@ int launch_sched_sort(int K, const int32_t* rec, int64_t M, uint32_t num_players
   // sort_nt >= 0: the caller's choice (WindowPipeline: loads-only between DP merges)
   const int nt = nt_e ? atoi(nt_e) : sort_nt >= 0 ? sort_nt : 0;
   const bool wide = bits <= 20 && rb_env == 10;
-  switch (K) {
-#define ANA_SORT_CASE(k)                                                                         \
-  case k:                                                                                        \
-    if (wide) sched_sort_k<k, 10, 0>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s); \
-    else if (nt == 1) sched_sort_k<k, 8, 1>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s); \
-    else if (nt == 2) sched_sort_k<k, 8, 2>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s); \
-    else sched_sort_k<k, 8, 0>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s); \
-    break;
-    ANA_SORT_CASE(1) ANA_SORT_CASE(2) ANA_SORT_CASE(3) ANA_SORT_CASE(4) ANA_SORT_CASE(5)
-#undef ANA_SORT_CASE
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+  const bool known = with_team_size(K, [&](auto k) {
+    constexpr int kK = decltype(k)::value;
+    if (wide) sched_sort_k<kK, 10, 0>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s);
+    else if (nt == 1) sched_sort_k<kK, 8, 1>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s);
+    else if (nt == 2) sched_sort_k<kK, 8, 2>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s);
+    else sched_sort_k<kK, 8, 0>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 }  // namespace ana

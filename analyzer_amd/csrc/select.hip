@@ -205,18 +205,13 @@ int64_t records_select_tiles(int64_t M) { return (M + kSelectTile - 1) / kSelect
 int launch_records_select_count(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P,
                                 const uint32_t* bitmap, uint32_t* counts, int64_t* offsets, hipStream_t s) {
   const int64_t tiles = records_select_tiles(M);
-  if (K < 1 || K > 5 || W < 5 * 2 * K + 2 || M < 0 || P < 0 || tiles > 0x7fffffffll) return (int)hipErrorInvalidValue;
+  if (K < 1 || K > kMaxTeamSize || W < 5 * 2 * K + 2 || M < 0 || P < 0 || tiles > 0x7fffffffll) return (int)hipErrorInvalidValue;
   const uint32_t* rw = reinterpret_cast<const uint32_t*>(rows);
   if (tiles > 0) {
-    switch (K) {
-#define ANA_SELECT_CASE(k)                                                                                   \
-  case k:                                                                                                    \
-    hipLaunchKernelGGL(select_count_kernel<k>, dim3((unsigned)tiles), dim3(kSelectThreads), 0, s, rec, rw, W, M, P, \
-                       bitmap, counts);                                                                      \
-    break;
-      ANA_SELECT_CASE(1) ANA_SELECT_CASE(2) ANA_SELECT_CASE(3) ANA_SELECT_CASE(4) ANA_SELECT_CASE(5)
-#undef ANA_SELECT_CASE
-    }
+    with_team_size(K, [&](auto k) {
+      hipLaunchKernelGGL(select_count_kernel<decltype(k)::value>, dim3((unsigned)tiles), dim3(kSelectThreads), 0, s,
+                         rec, rw, W, M, P, bitmap, counts);
+    });
   }
   hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(kSelectThreads), 0, s, counts, tiles, offsets);
   return (int)hipGetLastError();
@@ -226,18 +221,13 @@ int launch_records_select_emit(int K, const int32_t* rec, const float* rows, int
                                int64_t P, const uint32_t* bitmap, const int64_t* offsets, int32_t* hits,
                                int64_t nhits, hipStream_t s) {
   const int64_t tiles = records_select_tiles(M);
-  if (K < 1 || K > 5 || W < 5 * 2 * K + 2 || M < 0 || P < 0 || tiles > 0x7fffffffll) return (int)hipErrorInvalidValue;
+  if (K < 1 || K > kMaxTeamSize || W < 5 * 2 * K + 2 || M < 0 || P < 0 || tiles > 0x7fffffffll) return (int)hipErrorInvalidValue;
   if (tiles == 0 || nhits == 0) return 0;
   const uint32_t* rw = reinterpret_cast<const uint32_t*>(rows);
-  switch (K) {
-#define ANA_SELECT_CASE(k)                                                                                  \
-  case k:                                                                                                   \
-    hipLaunchKernelGGL(select_emit_kernel<k>, dim3((unsigned)tiles), dim3(kSelectThreads), 0, s, rec, rw, W, M, base, \
-                       P, bitmap, offsets, hits, nhits);                                                    \
-    break;
-    ANA_SELECT_CASE(1) ANA_SELECT_CASE(2) ANA_SELECT_CASE(3) ANA_SELECT_CASE(4) ANA_SELECT_CASE(5)
-#undef ANA_SELECT_CASE
-  }
+  with_team_size(K, [&](auto k) {
+    hipLaunchKernelGGL(select_emit_kernel<decltype(k)::value>, dim3((unsigned)tiles), dim3(kSelectThreads), 0, s, rec,
+                       rw, W, M, base, P, bitmap, offsets, hits, nhits);
+  });
   return (int)hipGetLastError();
 }
 

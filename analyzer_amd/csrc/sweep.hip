@@ -418,15 +418,10 @@ int launch_correct_records(int K, const int32_t* rec, int64_t M, float* rows, in
   const dim3 grid((unsigned)((M + T - 1) / T));
   const float2* d = reinterpret_cast<const float2*>(delta);
   const dim3 blk(T);
-  switch (K) {
-    case 1: hipLaunchKernelGGL(correct_records_kernel<1>, grid, blk, lds, st, rec, M, rows, orow, d, P); break;
-    case 2: hipLaunchKernelGGL(correct_records_kernel<2>, grid, blk, lds, st, rec, M, rows, orow, d, P); break;
-    case 3: hipLaunchKernelGGL(correct_records_kernel<3>, grid, blk, lds, st, rec, M, rows, orow, d, P); break;
-    case 4: hipLaunchKernelGGL(correct_records_kernel<4>, grid, blk, lds, st, rec, M, rows, orow, d, P); break;
-    case 5: hipLaunchKernelGGL(correct_records_kernel<5>, grid, blk, lds, st, rec, M, rows, orow, d, P); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+  const bool known = with_team_size(K, [&](auto k) {
+    hipLaunchKernelGGL(correct_records_kernel<decltype(k)::value>, grid, blk, lds, st, rec, M, rows, orow, d, P);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 static dim3 track_grid(int64_t P) {

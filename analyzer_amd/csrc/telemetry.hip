@@ -152,17 +152,11 @@ int launch_gen_events(int K, const GenEventParams& g, int64_t base, const int32_
                       const int64_t* evoff, int64_t M, int32_t* events, hipStream_t s) {
   if (M <= 0) return 0;
   const unsigned blocks = (unsigned)((M + 3) / 4 < 65536 ? (M + 3) / 4 : 65536);
-  switch (K) {
-#define ANA_GENEV_CASE(k)                                                                      \
-  case k:                                                                                      \
-    hipLaunchKernelGGL(gen_events_kernel<k>, dim3(blocks), dim3(256), 0, s, g, base, rec, evoff, \
-                       M, events);                                                             \
-    break;
-    ANA_GENEV_CASE(1) ANA_GENEV_CASE(2) ANA_GENEV_CASE(3) ANA_GENEV_CASE(4) ANA_GENEV_CASE(5)
-#undef ANA_GENEV_CASE
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+  const bool known = with_team_size(K, [&](auto k) {
+    hipLaunchKernelGGL(gen_events_kernel<decltype(k)::value>, dim3(blocks), dim3(256), 0, s, g, base, rec, evoff, M,
+                       events);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 int tele_impl() {
@@ -225,15 +219,8 @@ int launch_telemetry(int K, const TelemetryParams& tp, uint32_t* bad, hipStream_
   // silently timing the production kernel under their name
   if (dbg != 0 || span != kTeleMaxSpan || impl == 3) return (int)hipErrorNotSupported;
 #endif
-  switch (K) {
-    case 1: launch_tele_k<1>(tp, bad, s, impl, dbg, span); break;
-    case 2: launch_tele_k<2>(tp, bad, s, impl, dbg, span); break;
-    case 3: launch_tele_k<3>(tp, bad, s, impl, dbg, span); break;
-    case 4: launch_tele_k<4>(tp, bad, s, impl, dbg, span); break;
-    case 5: launch_tele_k<5>(tp, bad, s, impl, dbg, span); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+  const bool known = with_team_size(K, [&](auto k) { launch_tele_k<decltype(k)::value>(tp, bad, s, impl, dbg, span); });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 }  // namespace ana

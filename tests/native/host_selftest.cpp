@@ -125,6 +125,86 @@ static void run(int K, int64_t P, int64_t M, uint64_t seed) {
       }
   }
 
+  // C2 exchange: pack the rows of the first matches' slots, unpack them into a second roster
+  // and compare; the entries past the slots and the slots without a row carry id -1
+  {
+    const int64_t m = M < 200 ? M : 200, cap = m * S + 3;
+    std::vector<float> ent((size_t)cap * 33, -7.f), other(state.size(), NAN);
+    CHECK(host_pack_rows(rec.data(), K, m, status.data(), 1, st32.data(), P, ent.data(), cap) == 0);
+    CHECK(host_pack_rows(rec.data(), 0, m, status.data(), 1, st32.data(), P, ent.data(), cap) == -1);
+    CHECK(host_pack_rows(rec.data(), 6, m, status.data(), 1, st32.data(), P, ent.data(), cap) == -1);
+    host_unpack_rows(ent.data(), cap, other.data(), P);
+    std::vector<char> sent(P, 0);
+    for (int64_t e = 0; e < cap; ++e) {
+      const float* o = &ent[e * 33];
+      int32_t id;
+      memcpy(&id, o + 32, 4);
+      const int64_t i = e / S;
+      const int j = (int)(e % S);
+      bool row = false;
+      if (e < m * S) {
+        const uint32_t m0 = (uint32_t)rec[i * R + S];
+        const int n = j < K ? meta_n0(m0) : meta_n1(m0);
+        row = status[i] == kRated && (j < K ? j : j - K) < n && rec[i * R + j] >= 0 && rec[i * R + j] < P;
+      }
+      if (!row) {
+        CHECK(id == -1);
+        CHECK(o[0] == -7.f && o[31] == -7.f);  // no row written
+        continue;
+      }
+      CHECK(id == rec[i * R + j]);
+      CHECK(memcmp(o, &st32[(size_t)id * kRowFloats], kRowFloats * 4) == 0);
+      sent[id] = 1;
+    }
+    int64_t nsent = 0;
+    for (int64_t p = 0; p < P; ++p) {
+      nsent += sent[p];
+      for (int k = 0; k < kRowFloats; ++k) {
+        const float got = other[p * kRowFloats + k];
+        if (!sent[p]) CHECK(isnan(got));  // untouched
+        else if (k & 1) CHECK(got == 0.f);  // tags zeroed
+        else CHECK(memcmp(&got, &st32[p * kRowFloats + k], 4) == 0);
+      }
+    }
+    CHECK(nsent > 0);
+  }
+
+  // C2 race detector: the matches of level 1 share no player; a match and a successor do
+  {
+    std::vector<int64_t> round0, pair;
+    for (int64_t m = 0; m < M; ++m) {
+      if (level[m] == 1) round0.push_back(m);
+      for (int j = 0; j < S && pair.empty() && level[m] != 0; ++j) {
+        const uint32_t succ = link[m * S + j] & kMatchMask;
+        if (rec[m * R + j] >= 0 && succ != kNoMatch && (int64_t)succ > m) pair = {m, (int64_t)succ};
+      }
+    }
+    CHECK(!round0.empty() && pair.size() == 2);
+    std::vector<uint64_t> owner(P, 0);
+    int32_t flag = 0;
+    CHECK(host_check_round(rec.data(), K, round0.data(), (int64_t)round0.size(), P, 0, owner.data(), &flag) == 0);
+    CHECK(flag == 0);
+    CHECK(host_check_round(rec.data(), K, round0.data(), (int64_t)round0.size(), P, 1, owner.data(), &flag) == 0);
+    CHECK(flag == 0);  // a new round reuses the claims of the last one
+    if (pair.size() == 2) {
+      CHECK(host_check_round(rec.data(), K, pair.data(), 2, P, 2, owner.data(), &flag) == 0);
+      CHECK(flag == 1);
+    }
+    CHECK(host_check_round(rec.data(), 0, round0.data(), 1, P, 3, owner.data(), &flag) == -1);
+    CHECK(host_check_round(rec.data(), 6, round0.data(), 1, P, 3, owner.data(), &flag) == -1);
+  }
+
+  // reset_tags: every odd word (the tags) zeroed, mu / sigma untouched
+  {
+    std::vector<float> tagged = st32;
+    for (size_t i = 1; i < tagged.size(); i += 2) tagged[i] = 5.f;
+    host_reset_tags(tagged.data(), P);
+    for (size_t i = 0; i < tagged.size(); i += 2) {
+      CHECK(memcmp(&tagged[i], &st32[i], 4) == 0);
+      CHECK(tagged[i + 1] == 0.f);
+    }
+  }
+
   // telemetry
   GenEventParams ge{seed + 2, 0, 12};
   std::vector<int64_t> counts(M), evoff(M + 1, 0);

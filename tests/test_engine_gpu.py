@@ -44,7 +44,7 @@ def test_generators_bit_identical(gpu_device):
     a, b = make_roster(rs), make_roster(rs, device=gpu_device)
     assert torch.equal(a.state.view(torch.int32), b.state.cpu().view(torch.int32))
     assert torch.equal(a.attrs.view(torch.int32), b.attrs.cpu().view(torch.int32))
-    for K, skew in ((1, 1), (3, 1), (5, 1), (3, 2), (3, 3)):
+    for K, skew in ((1, 1), (2, 1), (3, 1), (4, 1), (5, 1), (3, 2), (3, 3)):
         ss = StreamSpec(team_size=K, seed=33, p_afk=0.1, p_tie=0.1, p_hot=0.3, p_uneven=0.1, skew=skew)
         ra = make_stream(ss, 20000, 5000, base=123)
         rb = make_stream(ss, 20000, 5000, base=123, device=gpu_device)
@@ -54,10 +54,13 @@ def test_generators_bit_identical(gpu_device):
 # 1 (P=20), 2 (P=300, 5000), 3 (P=70k) and 4 (P=17M) radix passes: every
 # combination of the fused first / last passes of the schedule sort
 # + micro-batches (<= 8192 slots): the one-workgroup LDS bitonic schedule
+# + every team size on both paths: K = 4 in one workgroup, K = 1, 2, 4 at the smallest
+#   windows of the sort path (> 8192 slots)
 @pytest.mark.parametrize("P,M,K", [(20, 3000, 3), (5000, 100000, 3), (300, 20000, 5),
                                    (70_000, 400_000, 3), (17_000_000, 300_000, 3),
                                    (50, 400, 3), (5000, 819, 5), (1_000_000, 1365, 3), (20, 1, 1),
-                                   (40, 700, 2)])
+                                   (40, 700, 2), (40, 700, 4), (40, 5000, 1), (40, 3000, 2),
+                                   (40, 1100, 4)])
 def test_schedule_matches_host(gpu_device, P, M, K):
     ss = StreamSpec(team_size=K, seed=P, p_afk=0.05, p_unsupported=0.05, p_uneven=0.05, p_hot=0.2)
     rec = make_stream(ss, M, P, K=K)
@@ -340,15 +343,23 @@ def test_sweep_kernels_match_host(gpu_device, scaled, resweep):
     assert torch.equal(base_rows(sh).nan_to_num(-7), sh2.nan_to_num(-7))
 
 
-@pytest.mark.parametrize("comm", ["fp32", "bf16", "fp16"])
-def test_record_correction_kernel_matches_host(gpu_device, comm):
+# M per team size: the host mirror alone changes 30416 / 46942 / 449336 / 78440 / 102330
+# entries at K = 1..5 (bf16), well over the test's floor of 10000
+@pytest.mark.parametrize("comm,K,M", [pytest.param("fp32", 3, 20000, id="fp32"),
+                                      pytest.param("bf16", 3, 20000, id="bf16"),
+                                      pytest.param("fp16", 3, 20000, id="fp16"),
+                                      pytest.param("bf16", 1, 6000, id="bf16-K1"),
+                                      pytest.param("bf16", 2, 4000, id="bf16-K2"),
+                                      pytest.param("bf16", 4, 3000, id="bf16-K4"),
+                                      pytest.param("bf16", 5, 3000, id="bf16-K5")])
+def test_record_correction_kernel_matches_host(gpu_device, comm, K, M):
     """K9 causal record correction (one thread per slot): device == host mirror on a
     rated window's records, NULL tracks, seeds, AFK / invalid matches and a prefix of
-    real messages (another slice's evidence) in every wire format."""
+    real messages (another slice's evidence) in every wire format, at every team size."""
     from analyzer_amd.ops.native import native
     from analyzer_amd.parallel.sweep import COMM_DTYPES, SweepMerger
 
-    P, M, K = 5000, 20000, 3
+    P = 5000
     rs = RosterSpec(num_players=P, seed=41, p_rated=0.4)
     start = make_roster(rs)
     other = start.clone()
@@ -464,6 +475,11 @@ def test_telemetry_device_generator_and_aggregation(gpu_device):
     assert torch.equal(td.evoff.cpu(), th.evoff) and torch.equal(td.events.cpu(), th.events)
     sd = aggregate(td, K)
     np.testing.assert_allclose(sd.cpu().numpy(), aggregate_reference(th, K), rtol=2e-5, atol=0.05)
+    for K in (1, 2, 4, 5):  # the device generator at the other team sizes
+        rec = make_stream(StreamSpec(team_size=K, seed=21 + K, p_uneven=0.2), 3000, 400, K=K)
+        th = make_telemetry(spec, rec, K)
+        td = make_telemetry(spec, rec.to(gpu_device), K)
+        assert torch.equal(td.evoff.cpu(), th.evoff) and torch.equal(td.events.cpu(), th.events)
 
 
 @pytest.mark.parametrize("impl", ["1", "0", "2"])
@@ -851,7 +867,8 @@ def _rccl_entry(rank, port, outdir, args):
 
 @pytest.mark.parametrize("P,M,K,skew", [(20, 3000, 3, 1), (5000, 100000, 3, 1), (300, 20000, 5, 1),
                                           (100_000, 400_000, 3, 2), (50, 400, 2, 1), (40, 700, 1, 1),
-                                          (1_000_000, 1_000_000, 4, 1)])
+                                          (1_000_000, 1_000_000, 4, 1), (20, 3000, 1, 1), (20, 3000, 2, 1),
+                                          (20, 3000, 4, 1)])
 def test_device_levels_match_host(gpu_device, P, M, K, skew):
     """K5 device levelizer (csrc/levels.hip, a dataflow over the radix or the
     micro-batch schedule) == the sequential host walk, level for level."""

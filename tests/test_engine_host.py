@@ -1,4 +1,6 @@
 """Batched engine (C++ host mirror) == per-object reference-semantics rater."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -201,3 +203,61 @@ def test_warm_rows_host_is_a_no_op():
     with pytest.raises(RuntimeError):
         native().warm_rows(roster.state, torch.zeros(8, dtype=torch.int32))
 
+
+
+def _team_size_calls():
+    """Every binding that takes a team size, on tiny CPU operands (M = 2) that are valid
+    for the K they are built for: name -> call(native module, K)."""
+    i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32)  # noqa: E731
+    f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32)  # noqa: E731
+    M, P = 2, 4
+    rec = lambda K: i32(M, 2 * K + 2)  # noqa: E731
+    none = torch.empty(0, dtype=torch.int64)
+    cdf = [1 << 29] * 6 + [0xffffffff]
+
+    def rate(n, K):
+        S = 2 * K
+        n.rate(rec(K), K, i32(0), i32(0), f32(P, 32), f32(P, 4), f32(0), f32(M), torch.zeros(M, dtype=torch.uint8),
+               f32(M, S), f32(M, S), f32(M, S), f32(M, S), f32(M, S), i32(0), f32(31), 1e6, 100.0, 500.0, False, 1, 1,
+               True, none, none.to(torch.int32), none.to(torch.float32), 0, 0, 0, 0, 64, False, [0, 1, 0, -1, 0, 2])
+
+    return {
+        "gen_stream": lambda n, K: n.gen_stream(rec(K), K, 1, 0, P, max(K, 1), cdf, 0, 0, 0, 0, 0, 1, 1),
+        "levels": lambda n, K: n.levels(rec(K), K, P),
+        "schedule": lambda n, K: n.schedule(rec(K), K, P, i32(M, 2 * K), i32(M), torch.empty(0, dtype=torch.uint8),
+                                            i32(0), False, 0, -1),
+        "rate": rate,
+        "gen_events": lambda n, K: n.gen_events(rec(K), K, torch.zeros(M + 1, dtype=torch.int64), 1, 0, 0, 0, i32(0, 2)),
+        "telemetry": lambda n, K: n.telemetry(torch.zeros(M + 1, dtype=torch.int64), i32(0, 2), K,
+                                              f32(M, 2 * K, 8), i32(1)),
+        "correct_records": lambda n, K: n.correct_records(rec(K), K, f32(M, 64), f32(P, 16)),
+        "pack_rows": lambda n, K: n.pack_rows(rec(K), K, torch.zeros(M, dtype=torch.uint8), f32(P, 32),
+                                              f32(M * 2 * K, 33)),
+        "check_round": lambda n, K: n.check_round(rec(K), K, torch.zeros(M, dtype=torch.int64), 0,
+                                                  torch.zeros(P, dtype=torch.int64), i32(1)),
+        "write_record_file": lambda n, K: n.write_record_file(os.devnull, rec(K), K),
+        "records_digest": lambda n, K: n.records_digest(f32(M, 64), K, torch.zeros(1 << 16, dtype=torch.float64),
+                                                        torch.zeros(3 + 10 * K, dtype=torch.float64)),
+        "records_select": lambda n, K: n.records_select(rec(K), f32(M, 64), 0, P, i32(1)),
+        "preview": lambda n, K: n.preview(rec(K), K, f32(P, 32), None, f32(31), 1e6, 500.0),
+        "balance": lambda n, K: n.balance(i32(M, 2 * K), K, f32(P, 32), None, f32(31), 0, 1e6, 500.0),
+        "matchmake_geometry": lambda n, K: n.matchmake_geometry(K),
+        "split_masks": lambda n, K: n.split_masks(K),
+    }
+
+
+@pytest.mark.parametrize("K", [0, 6])
+@pytest.mark.parametrize("name", sorted(_team_size_calls()))
+def test_bindings_reject_team_size_out_of_range(name, K):
+    """One answer for a team size outside 1..5 in every entry point: an error that says
+    so, before anything runs (and, as a control, no such error at K = 1 and 5)."""
+    from analyzer_amd.ops.native import native
+
+    call = _team_size_calls()[name]
+    with pytest.raises(RuntimeError, match=r"1\.\.5"):
+        call(native(), K)
+    for ok in (1, 5):
+        try:
+            call(native(), ok)
+        except RuntimeError as e:  # (records_digest: "device rows" on the CPU)
+            assert "1..5" not in str(e), e

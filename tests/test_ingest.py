@@ -33,6 +33,16 @@ def test_bad_file_is_rejected(tmp_path):
         native().RecordReader(str(p), 10, 2, False)
 
 
+@pytest.mark.parametrize("K", [0, 6])
+def test_write_record_file_rejects_team_size_out_of_range(tmp_path, K):
+    from analyzer_amd.ops.native import native
+
+    path = tmp_path / "k.rec"
+    with pytest.raises(RuntimeError, match=r"K .*must be 1\.\.5"):
+        native().write_record_file(str(path), torch.zeros((2, 2 * K + 2), dtype=torch.int32), K)
+    assert not path.exists()
+
+
 def test_rate_file_equals_direct_rating(tmp_path):
     rec, K, P = _data(M=900)
     path = str(tmp_path / "s.rec")

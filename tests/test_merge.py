@@ -381,6 +381,16 @@ def test_host_prefix_delta_within_budget(wire):
     check_prefix_delta("cpu", wire)
 
 
+def test_prefix_delta_rejects_a_short_seed_table():
+    """The kernel indexes vst by tier + 1 (31 tiers): a shorter table must not reach it."""
+    P = 2
+    s0, attrs, delta = torch.zeros(P, 16), torch.zeros(P, 4), torch.empty(P, 16)
+    prefix = torch.zeros(P, 14, dtype=torch.bfloat16)
+    with pytest.raises(RuntimeError, match="vst must have 31 entries"):
+        native().prefix_delta(s0, prefix, attrs, _vst("cpu")[:30].contiguous(), US, delta)
+    native().prefix_delta(s0, prefix, attrs, _vst("cpu"), US, delta)  # the whole table passes
+
+
 @pytest.mark.parametrize("K", [1, 2, 3, 4, 5])
 def test_host_record_correction_within_budget(K):
     check_records("cpu", K)

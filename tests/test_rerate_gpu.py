@@ -15,7 +15,8 @@ from analyzer_amd.runtime.rerate import _Digest, window_digest
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("K,M,P", [(3, 200_000, 20_000), (5, 50_000, 5_000), (1, 3_000, 400), (3, 1, 10)])
+@pytest.mark.parametrize("K,M,P", [(3, 200_000, 20_000), (5, 50_000, 5_000), (1, 3_000, 400), (3, 1, 10),
+                                   (2, 3_000, 400), (4, 3_000, 400)])
 def test_device_digest_matches_fp64_torch(gpu_device, K, M, P):
     roster = make_roster(RosterSpec(num_players=P, seed=3, p_rated=0.4), device=gpu_device)
     rec = make_stream(StreamSpec(team_size=K, seed=4, p_afk=0.05), M, P, K=K, device=gpu_device)
