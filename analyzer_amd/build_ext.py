@@ -28,7 +28,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 HIP_SOURCES = ["kernels.hip", "radix_sort.hip", "dataflow.hip", "sweep.hip", "telemetry.hip", "levels.hip",
-               "digest.hip", "select.hip", "ladder.hip", "matchmake.hip"]
+               "digest.hip", "select.hip", "ladder.hip", "matchmake.hip", "career.hip"]
 # per-file device flags.  The executor's divisions/sqrt take the 1-ulp hardware
 # paths (v_rcp_f32 instead of the ~10-instruction IEEE division expansion: -9%
 # static instructions); NaN/Inf semantics are untouched (no -ffinite-math-only),
@@ -38,6 +38,8 @@ HIP_FLAGS = {n: ["-fapprox-func", "-freciprocal-math", "-fno-signed-zeros"]
 # the matchmaker's split choice is bit-identical to the host mirror's: no FMA contraction, every
 # fp32 operation is the one written (csrc/matchmake_core.h)
 HIP_FLAGS["matchmake.hip"] = ["-ffp-contract=off"]
+# a career's score is the one IEEE subtraction the host mirror does (csrc/career_core.h)
+HIP_FLAGS["career.hip"] = ["-ffp-contract=off"]
 CPP_SOURCES = ["host.cpp", "ingest.cpp", "batch_host.cpp", "telemetry_file.cpp", "bindings.cpp"]
 
 

@@ -14,6 +14,7 @@
 #include <tuple>
 #include <vector>
 
+#include "career_core.h"
 #include "common.h"
 #include "gen_core.h"
 #include "host.h"
@@ -899,6 +900,55 @@ Tensor records_select(Tensor rec, Tensor rows, int64_t base, int64_t P, Tensor b
   return hits;
 }
 
+// K13 (career.hip; host mirror host.cpp host_careers_add): folds the games of one window -- rec
+// [M, 2K+2] joined with its packed output rows [M, W], base the global index of match 0 -- into
+// the career table [P, 16] int32 in place (career_core.h).  Dispatches on the tensors' device;
+// the device path is four stream-ordered steps (keys, sort, fold, stitch) without a host read.
+void careers_add(Tensor table, Tensor rec, Tensor rows, int64_t base, int64_t P, int64_t track, int64_t score,
+                 int64_t modes) {
+  const auto dev = table.device();
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "careers_add: rec must be [M, 2K+2]");
+  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t M = check_rec(rec, K, dev, "careers_add");
+  check(rows, "rows", torch::kFloat32, dev);
+  TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "careers_add: P must fit in int32");
+  check_rows(table, "table", P, ana::kCareerWords, dev, torch::kInt32);
+  TORCH_CHECK(rows.dim() == 2 && rows.size(0) == M && rows.size(1) >= 10 * K + 2 && rows.size(1) % 4 == 0,
+              "careers_add: rows must be the packed [M, W] output rows of rec's matches");
+  TORCH_CHECK(base >= 0, "careers_add: base must be >= 0");
+  TORCH_CHECK(track == ana::kCareerShared || track == ana::kCareerMode, "careers_add: unknown track ", track);
+  TORCH_CHECK(score == ana::kLadderConservative || score == ana::kLadderMu, "careers_add: unknown score ", score);
+  TORCH_CHECK(modes >= 0 && (modes & ~(int64_t)ana::kCareerAllModes) == 0,
+              "careers_add: the modes mask must name modes 0..5");
+  TORCH_CHECK(M * 2 * K <= ana::kMaxSlots, "careers_add: a window holds at most ", ana::kMaxSlots, " slots");
+  if (M == 0 || P == 0) return;
+  if (!dev.is_cuda()) {
+    TORCH_CHECK(ana::host_careers_add((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, base,
+                                      P, (int)track, (int)score, (uint32_t)modes, table.data_ptr<int32_t>()) == 0,
+                "careers_add: bad arguments");
+    return;
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(rec.data_ptr()) % (K % 2 == 0 ? 8 : 16) == 0 &&
+                  reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0,
+              "careers_add: rec, rows and table must be 16-B aligned");
+  const hipStream_t s = stream_of(table);
+  const int64_t n = M * 2 * K;
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
+  Tensor keys = torch::empty({n}, i32), vals = torch::empty({n}, i32);
+  Tensor events = torch::empty({n, (int64_t)ana::kCareerEventWords}, i32);
+  check_hip(ana::launch_career_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                    (int)track, (int)score, (uint32_t)modes, u32p(keys), u32p(vals), u32p(events), s),
+            "career_keys");
+  int bits = 1;
+  while ((P >> bits) != 0) ++bits;  // bit_length(P): the key P of a slot that is no game sorts last
+  const auto sorted = sort_pairs_on_stream(keys, vals, n, bits, s);
+  Tensor edges = torch::empty({(int64_t)ana::career_edge_bytes(n)}, i32.dtype(torch::kUInt8));
+  check_hip(ana::launch_career_fold(u32p(sorted[0]), u32p(sorted[1]), u32p(events), n, (int)K, base, P,
+                                    table.data_ptr<int32_t>(), edges.data_ptr<uint8_t>(), s),
+            "career_fold");
+}
+
 // K11 (ladder.hip; host mirror host.cpp host_ladder): the ladders of the tracks of ``mask``
 // (bit t = granule t) of a roster's state [P, 32], as [order, score, rank] per track in
 // ascending track order: order int32 [R] (best first), score fp32 [R], rank int32 [P]
@@ -1160,6 +1210,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vst"), py::arg("mode"), py::arg("unknown_sigma"));
   m.def("matchmake_geometry", &matchmake_geometry, "K12: (lanes per lobby, lobbies per wave, lobbies per workgroup)");
   m.def("split_masks", &split_masks, "K12: the team-0 masks of the splits of a 2K lobby, in index order");
+  m.def("careers_add", &careers_add, "K13: fold one window (rec [M, 2K+2] joined with its packed rows [M, W]) into the "
+        "career table [P, 16] int32 in place: careers_add(table, rec, rows, base, P, track, score, modes)");
+  m.attr("CAREER_WORDS") = ana::kCareerWords;
+  m.attr("CAREER_TILE") = ana::kCareerTile;
+  m.attr("MAX_SLOTS") = (int64_t)ana::kMaxSlots;
   m.attr("LADDER_CONSERVATIVE") = (int)ana::kLadderConservative;
   m.attr("LADDER_MU") = (int)ana::kLadderMu;
   m.attr("HIT_WORDS") = ana::kHitWords;

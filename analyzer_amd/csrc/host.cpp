@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "career_core.h"
 #include "gen_core.h"
 #include "ladder_core.h"
 #include "matchmake_core.h"
@@ -353,6 +354,40 @@ int64_t records_select_host(int K, const int32_t* rec, const float* rows, int64_
   int64_t n = -1;
   with_team_size(K, [&](auto k) { n = records_select_k<decltype(k)::value>(rec, rows, W, M, base, P, bitmap, hits); });
   return n;
+}
+
+// K13: the games in (match, slot) order, each folded into its player's row as a run of one
+template <int K>
+static void careers_add_k(const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base, int64_t P,
+                          int32_t track, int32_t score, uint32_t modes, int32_t* table) {
+  constexpr int S = 2 * K;
+  for (int64_t m = 0; m < M; ++m) {
+    const int32_t* r = rec + m * (S + 2);
+    const uint32_t mask = career_mask<K>(r, P, modes);
+    if (!mask) continue;  // the row is only read for a candidate
+    uint32_t row[5 * S + 2];
+    memcpy(row, rows + m * W, sizeof(row));
+    const uint32_t st = select_row_status<K>(row);
+    if (!select_status(st)) continue;
+    const int f = career_field(track);
+    for (int j = 0; j < S; ++j) {
+      if (!((mask >> j) & 1u)) continue;
+      uint32_t ev[kCareerEventWords];
+      career_event<K>(r, j, st, row[f * S + j], row[(f + 1) * S + j], row[5 * S], score, ev);
+      career_row_add(table + (int64_t)r[j] * kCareerWords, career_game(ev[0], ev[1], base + m));
+    }
+  }
+}
+
+int host_careers_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base, int64_t P,
+                     int track, int score, uint32_t modes, int32_t* table) {
+  if (W < 5 * 2 * K + 2 || M < 0 || base < 0 || P < 0 || P > 0x7fffffffll ||
+      (track != kCareerShared && track != kCareerMode) || (score != kLadderConservative && score != kLadderMu) ||
+      (modes & ~kCareerAllModes))
+    return -1;
+  return with_team_size(K, [&](auto k) {
+    careers_add_k<decltype(k)::value>(rec, rows, W, M, base, P, track, score, modes, table);
+  }) ? 0 : -1;
 }
 
 // K11: the device's three stages on one track -- keys in id order, a stable sort of the

@@ -60,6 +60,11 @@ int64_t records_select_host(int K, const int32_t* rec, const float* rows, int64_
 // bit-identical to the device.  Returns R, the number of ranked players (-1: bad arguments).
 int64_t host_ladder(const float* state, int64_t P, int track, int score, float max_sigma, int32_t* order,
                     float* score_out, int32_t* rank);
+// K13 host mirror (career_core.h): the games of rec [M][2K+2] joined with rows [M][W], in
+// (match, slot) order, folded into table [P][kCareerWords], bit-identical to the device.
+// -1: bad arguments.
+int host_careers_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base, int64_t P,
+                     int track, int score, uint32_t modes, int32_t* table);
 // K12 host mirror (matchmake_core.h); out / records as launch_preview / launch_balance /
 // launch_queue_keys (kernels.h) lay them out; attrs may be null.  preview runs rate's own
 // fp64 path (status and quality are the bits host_rate writes); balance chooses the split in

@@ -84,6 +84,21 @@ int launch_balance(int K, const int32_t* lobbies, int64_t L, const float* state,
 int launch_queue_keys(const int32_t* queue, int64_t Q, const float* state, const float* attrs, const float* vst,
                       int64_t P, int mode, float unknown_sigma, uint32_t* keys, uint32_t* vals, hipStream_t s);
 
+// K13 careers (career.hip, career_core.h): one window rec [M][2K+2] joined with its packed rows
+// [M][W] (alignment as for K10), M * 2K <= kMaxSlots, folded into table [P][kCareerWords] (16-B
+// aligned).  career_keys writes per slot i = m * 2K + j the sort key (the player of a game, else
+// P), vals[i] = i and the game's event (events: 2 words per slot, 8-B aligned); the pairs are
+// sorted with launch_radix_sort_pairs on bit_length(P) bits; career_fold takes the sorted pairs
+// [n = M * 2K] and adds every player's run to its row (edges: career_edge_bytes(n) bytes, 16-B
+// aligned).  base: global index of match 0; track: CareerTrack; score: LadderScore; modes: bit
+// per mode.  Everything is stream-ordered and only reads rec and rows.
+constexpr int kCareerTile = 4096;  // sorted elements per workgroup of the fold
+size_t career_edge_bytes(int64_t n);
+int launch_career_keys(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, int track,
+                       int score, uint32_t modes, uint32_t* keys, uint32_t* vals, uint32_t* events, hipStream_t s);
+int launch_career_fold(const uint32_t* keys, const uint32_t* vals, const uint32_t* events, int64_t n, int K,
+                       int64_t base, int64_t P, int32_t* table, void* edges, hipStream_t s);
+
 // Stable LSD radix sort of (key, value) pairs on the low ``bits`` key bits
 // (radix_sort.hip).  Ping-pongs between the two buffer pairs; *result_in_alt
 // says which holds the result.  ws: radix_sort_workspace_bytes(n) bytes.

@@ -20,6 +20,10 @@ for K = 4, 5).  ``records="resident"`` keeps them where the executor writes them
   ``records_select`` kernel (csrc/select.hip, K10) against a bitmap of the queried
   players; hits come out in ascending (match, slot) order, the same bits on every run.
   On N ranks it returns the local hits (merging across ranks is up to the caller).
+* ``careers(num_players, rec_of)`` folds the same join into one 64-B row per player
+  (``ops/careers.py`` ``CareerTable``, csrc/career.hip, K13): games, wins, first and
+  last match, peak and trough, streaks and the quality sum of every player at once,
+  without the hits ever leaving the device.  On N ranks it covers the local blocks.
 * ``export`` / ``load`` move the filled rows through two pinned slots on a copy stream
   into one flat file plus a small JSON header; the round trip is bit-identical.  This
   is how an arena is persisted: checkpoints do not hold arena rows, so a resumed run
@@ -36,6 +40,7 @@ from typing import Callable, Dict, Iterator, Optional, Sequence, Tuple, Union
 
 import torch
 
+from ..ops.careers import CareerTable
 from ..ops.native import native
 from ..ops.rate import RateResult, Roster
 
@@ -203,6 +208,16 @@ class RecordArena:
             parts.append(records_select(rec, self.rows[a:a + hi - lo], lo, num_players, bitmap))
         hits = torch.cat(parts) if parts else torch.empty((0, 12), dtype=torch.int32, device=self.device)
         return hits_columns(hits)
+
+    def careers(self, num_players: int, rec_of: Callable[[int, int], torch.Tensor], **kw) -> CareerTable:
+        """The career table (``ops/careers.py``) of all ``num_players`` players over the
+        filled windows, walked as ``history`` walks them; ``kw``: ``track``, ``score``,
+        ``modes`` of ``CareerTable``.  On N ranks it covers this rank's blocks only."""
+        table = CareerTable(num_players, self.device, **kw)
+        for lo, hi in self.windows():
+            a = int(self.local_row(lo))
+            table.add(rec_of(lo, hi), self.rows[a:a + hi - lo], lo, K=self.K)
+        return table
 
     # ------------------------------------------------------------ sizing
     @staticmethod

@@ -411,6 +411,13 @@ def _timeline(hist: dict, player: int) -> dict:
     return line
 
 
+def career_lines(table, ids) -> list:
+    """One JSON-ready dict per player of ``ids`` from a ``CareerTable`` (ops/careers.py)."""
+    cols = {name: col.cpu().tolist() for name, col in table.lookup(list(ids)).items()}
+    return [dict({"career": int(p), "track": table.track, "score": table.score},
+                 **{name: _num(vals[i]) for name, vals in cols.items()}) for i, p in enumerate(ids)]
+
+
 def _num(v: float):
     return None if v != v else v  # NaN -> null
 
@@ -481,6 +488,13 @@ def main(argv=None) -> int:
                          "device-resident arena (prints the arena's sizing plan first; exit code 2 if it does not fit)")
     ap.add_argument("--history", default=None, metavar="ID[,ID...]",
                     help="with --records resident: print each player's timeline after the run (JSON lines)")
+    ap.add_argument("--careers", default=None, metavar="ID[,ID...]",
+                    help="with --records resident: print each player's career after the run (JSON lines): games, "
+                         "wins, first / last match, peak and trough score, streaks, mean quality")
+    ap.add_argument("--careers-track", default="shared", choices=["shared", "mode"],
+                    help="with --careers: score the shared track or each match's mode track")
+    ap.add_argument("--careers-modes", default=None, metavar="MODE[,MODE...]",
+                    help="with --careers: count only the matches of these modes (default: all)")
     ap.add_argument("--export-records", default=None, metavar="PATH",
                     help="with --records resident: write the arena to PATH (+ PATH.json; .rN appended on N ranks)")
     ap.add_argument("--arena-free-bytes", type=float, default=None,
@@ -503,6 +517,19 @@ def main(argv=None) -> int:
     resident = args.records == "resident"
     if (args.history or args.export_records) and not resident:
         ap.error("--history and --export-records need --records resident")
+    if args.careers and not resident:
+        ap.error("--careers needs --records resident")
+    if (args.careers_modes or args.careers_track != "shared") and not args.careers:
+        ap.error("--careers-track and --careers-modes need --careers")
+    career_modes = [m.strip() for m in (args.careers_modes or "").split(",") if m.strip()] or None
+    try:
+        career_ids = [int(p) for p in (args.careers or "").split(",") if p.strip()]
+        for m in career_modes or ():
+            mode_index(m)
+    except ValueError as e:
+        ap.error("--careers: %s" % e)
+    if any(p < 0 or p >= spec.players for p in career_ids):
+        ap.error("--careers ids must lie in [0, %d)" % spec.players)
     if args.ladder_rank and not args.ladder:
         ap.error("--ladder-rank needs --ladder")
     ladder_tracks = [t.strip() for t in (args.ladder or "").split(",") if t.strip()]
@@ -569,6 +596,11 @@ def main(argv=None) -> int:
         hist = arena.history(ids, spec.players, stream_records(spec, arena.device))  # this rank's hits
         for p in ids:
             print(json.dumps(dict(_timeline(hist, p), rank=rank)), flush=True)
+    if career_ids:
+        table = arena.careers(spec.players, stream_records(spec, arena.device), track=args.careers_track,
+                              modes=career_modes)  # this rank's blocks
+        for line in career_lines(table, career_ids):
+            print(json.dumps(dict(line, rank=rank)), flush=True)
     if ladder_tracks and rank == 0:  # the roster is replicated after the last merge
         for line in ladder_lines(roster, ladder_tracks, args.ladder_top, ladder_ids):
             print(json.dumps(line), flush=True)
