@@ -244,6 +244,8 @@ class EngineConfig:
         "ANA_SCHED_SMALL": "micro-batch schedule: hash lists (default) or bitonic sort",
         "ANA_SORT_RB / ANA_SORT_NT": "radix-sort tile rows / non-temporal loads (tuning)",
         "ANA_SCHED_RUNS": "last schedule pass: run-end table (1, default) or digit offsets + fix-up (0)",
+        "ANA_SCHED_CHAIN": "schedule of <= 2^20 players: one partition + per-bucket LDS chain pass (1; default "
+                           "where a bucket is short enough) or three LSD passes (0)",
     }
 
     def rate_knobs(self) -> list:

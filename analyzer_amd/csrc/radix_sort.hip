@@ -23,6 +23,13 @@
 // its LDS neighbours instead of the sorted pairs (only run-boundary pairs go out,
 // for the fix-up).  For 10M 3v3 matches that drops a 480-MB key/value write, the
 // re-reads of it and a separate 720-MB link pass.
+//
+// Rosters of <= 2^20 players (round 7) need only the first of those passes: one stable
+// partition by the key bits above the low 12, then sched_chain -- one workgroup per bucket
+// sorts its tiles in LDS and chains each player's slots through a last-occurrence table
+// (4 launches and ~1.84 GB per 10M 3v3 window instead of 9 and ~3.0 GB; 1.22-1.25 ms alone
+// against 1.60-1.64, the config 2 step 0.10-0.12 ms shorter, profiles/r7/sched_chain_ab.log).
+// Larger rosters keep the three LSD passes; ANA_SCHED_CHAIN=0 selects them for A/B.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -100,7 +107,7 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t x, uint32_t* w
 // LDS key array, instead of every slot re-decoding its whole match.
 template <int KS>
 __device__ __forceinline__ void decode_tile_keys(const int32_t* __restrict__ rec, uint32_t kend,
-                                                 int64_t base, int64_t n, uint32_t* lk) {
+                                                 int64_t base, int64_t n, uint32_t* lk, uint32_t knone) {
   constexpr int S = 2 * KS, R = S + 2;
   const uint32_t lo = (uint32_t)base;  // slots < kMaxSlots
   const uint32_t hi = (uint32_t)(base + kTile < n ? base + kTile : n);
@@ -125,7 +132,7 @@ __device__ __forceinline__ void decode_tile_keys(const int32_t* __restrict__ rec
       const uint32_t slot = m * S + j;
       const int pos = j < KS ? j : j - KS;
       const bool in_roster = pos < (j < KS ? meta_n0(m0) : meta_n1(m0));
-      if (slot >= lo && slot < hi) lk[slot - lo] = rates && in_roster ? (uint32_t)r[j] : kend;
+      if (slot >= lo && slot < hi) lk[slot - lo] = rates && in_roster ? (uint32_t)r[j] : knone;
     }
   }
 }
@@ -144,7 +151,8 @@ struct SchedInit {
 template <int KS, int RB = 8, int NT = 0>
 __global__ void __launch_bounds__(kThreads)
 radix_upsweep(const uint32_t* __restrict__ keys, const int32_t* __restrict__ rec, uint32_t kend,
-              int64_t n, int shift, uint32_t* __restrict__ counts, int64_t tiles, SchedInit init = {}) {
+              int64_t n, int shift, uint32_t* __restrict__ counts, int64_t tiles, SchedInit init = {},
+              uint32_t knone = 0u) {
   constexpr int kR = 1 << RB;
   __shared__ uint32_t hist[kWaves][kR];
   __shared__ uint32_t lkeys[KS > 0 ? kTile : 1];
@@ -163,7 +171,7 @@ radix_upsweep(const uint32_t* __restrict__ keys, const int32_t* __restrict__ rec
       if (tid == 0 && init.epoch_bump) init.epoch_bump[0] += 1;
     }
   }
-  if constexpr (KS > 0) decode_tile_keys<KS>(rec, kend, base, n, lkeys);
+  if constexpr (KS > 0) decode_tile_keys<KS>(rec, kend, base, n, lkeys, knone ? knone : kend);
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < kItems; ++k) {
@@ -252,7 +260,7 @@ radix_downsweep(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ v
                 const uint32_t* __restrict__ counts, const uint32_t* __restrict__ totals,
                 int64_t tiles, int slots_per_match, uint32_t* __restrict__ link,
                 uint32_t vlo = 0u, uint32_t vhi = 0xffffffffu, int bounds = 1,
-                RunEnds* __restrict__ bnd = nullptr, int nd = 0) {
+                RunEnds* __restrict__ bnd = nullptr, int nd = 0, uint32_t knone = 0u) {
   constexpr int kR = 1 << RB;
   constexpr int DPT = kR >= kThreads ? kR / kThreads : 1;  // digits per thread in the scans
   static_assert(kR % kThreads == 0 || kThreads % kR == 0, "radix and block must divide");
@@ -276,7 +284,8 @@ radix_downsweep(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ v
     for (int j = 0; j < DPT; ++j)
       if (tid * DPT + j < kR) gstart[tid * DPT + j] = v[j] + counts[(int64_t)(tid * DPT + j) * tiles + tile];
   }
-  if constexpr (KS > 0) decode_tile_keys<KS>(rec, kend, base, n, sval);  // sval: scratch until the scatter
+  if constexpr (KS > 0)  // sval: scratch until the scatter
+    decode_tile_keys<KS>(rec, kend, base, n, sval, knone ? knone : kend);
   __syncthreads();
 
   // wave wv owns tile elements [wv*kItems*64, (wv+1)*kItems*64) in (item, lane) order,
@@ -525,6 +534,193 @@ sched_runs_fixup(const RunEnds* __restrict__ bnd, int64_t tiles, int nd, const i
   atomicAnd(&link[pr.vl], ~kMatchMask | (me.vf / (uint32_t)slots_per_match));
 }
 
+// The chain pass (sched_sort_k, rosters of <= 2^20 players).  The links need less than a
+// sorted array: per slot the match of the same player's next slot and a has-earlier
+// bit.  After ONE stable partition by the key bits above `low` (<= 12) every bucket holds
+// at most 2^low players in slot (time) order, and one workgroup per bucket chains them:
+// it walks its bucket tile by tile, sorts each tile stably by the low key bits in LDS
+// (two 6-bit rounds of the downsweep's ballot ranking, no global traffic) and keeps a
+// last-occurrence table T[2^low] in LDS -- per player the last slot seen and its
+// has-earlier bit (slots < 2^28: one word).  In the sorted tile
+//   an element with a successor in the tile  writes link[slot] = succ match | has_pred,
+//   the first of a player's run              writes the link T deferred for that player,
+//   the last of a run                        goes into T, its link deferred,
+// and after the last tile T is flushed with kNoMatch links.  Every link is written once,
+// with plain stores (L2 write combining, see radix_downsweep); no workgroup waits on
+// another.  KS > 0: no partition in front (top = 0, <= 4096 players): the one workgroup
+// decodes its keys from the records and does the SchedInit duties.
+constexpr int kChainLowBits = 12;
+constexpr int kChainRB = 6;
+constexpr uint32_t kChainEmpty = 0xffffffffu;
+constexpr bool kChainDefault = true;  // ANA_SCHED_CHAIN overrides (launch_sched_sort)
+
+// one stable ranking round of the tile held in registers ((wave, item, lane) order = tile
+// order) by kChainRB key bits at `shift`, scattered into skey / sval
+__device__ __forceinline__ void chain_sort_round(const uint32_t (&key)[kItems], const uint32_t (&val)[kItems],
+                                                 int shift, uint32_t* skey, uint32_t* sval,
+                                                 uint32_t (*wcnt)[1 << kChainRB], uint32_t* tstart,
+                                                 uint32_t* wsum) {
+  constexpr int kR = 1 << kChainRB;
+  static_assert(kR <= kThreads, "one digit per thread in the scan");
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  for (int i = tid; i < kWaves * kR; i += kThreads) (&wcnt[0][0])[i] = 0u;
+  __syncthreads();
+  uint32_t rank[kItems];
+#pragma unroll
+  for (int it = 0; it < kItems; ++it) {
+    const uint32_t d = (key[it] >> shift) & (kR - 1);
+    uint64_t peers = ~0ull;
+#pragma unroll
+    for (int b = 0; b < kChainRB; ++b) {
+      const uint64_t bal = __ballot((d >> b) & 1u);
+      peers &= ((d >> b) & 1u) ? bal : ~bal;
+    }
+    const uint32_t before = (uint32_t)__popcll(peers & lt_mask);
+    const uint32_t run = wcnt[wv][d];
+    rank[it] = run + before;
+    if (before == (uint32_t)__popcll(peers) - 1u) wcnt[wv][d] = run + (uint32_t)__popcll(peers);
+  }
+  __syncthreads();
+  {  // per-digit prefix over waves, then tile-local digit starts
+    uint32_t v[1];
+    uint32_t s = 0;
+    if (tid < kR) {
+#pragma unroll
+      for (int w = 0; w < kWaves; ++w) {
+        const uint32_t c = wcnt[w][tid];
+        wcnt[w][tid] = s;
+        s += c;
+      }
+    }
+    v[0] = s;
+    digits_exclusive_scan<1>(v, wsum, nullptr);
+    if (tid < kR) tstart[tid] = v[0];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < kItems; ++it) {
+    const uint32_t d = (key[it] >> shift) & (kR - 1);
+    const uint32_t pos = tstart[d] + wcnt[wv][d] + rank[it];
+    skey[pos] = key[it];
+    sval[pos] = val[it];
+  }
+  __syncthreads();
+}
+
+// (84 KB of LDS: one workgroup per CU, two waves per SIMD.  The link loops are unrolled by 2
+// only: fully unrolled the compiler takes 236 VGPRs, and two such waves no longer fit on a
+// SIMD beside a wave of the executor; 164 do)
+template <int KS, int NT>
+__global__ void __launch_bounds__(kThreads)
+sched_chain(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
+            const int32_t* __restrict__ rec, uint32_t kend, int64_t n, int low,
+            const uint32_t* __restrict__ totals, int slots_per_match, uint32_t* __restrict__ link,
+            uint32_t vlo, uint32_t vhi, int64_t matches, SchedInit init) {
+  constexpr int kR = 1 << kChainRB;
+  __shared__ uint32_t skey[kTile];
+  __shared__ uint32_t sval[kTile];
+  __shared__ uint32_t last_seen[1 << kChainLowBits];  // T: slot | kLinkHasPred, kChainEmpty
+  __shared__ uint32_t wcnt[kWaves][kR];
+  __shared__ uint32_t tstart[kR];
+  __shared__ uint32_t wsum[kWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint32_t lmask = (1u << low) - 1u;
+  for (int e = tid; e <= (int)lmask; e += kThreads) last_seen[e] = kChainEmpty;
+  // this workgroup's bucket: [start, start + cnt) of the partitioned pairs
+  int64_t start = 0, cnt = n;
+  if constexpr (KS > 0) {
+    if (init.deps)
+      for (int64_t m = tid; m < matches; m += kThreads) init.deps[m] = 0;
+    if (tid < init.nz) init.ctrl[tid] = 0u;
+    if (tid == 0 && init.epoch_bump) init.epoch_bump[0] += 1;
+  } else {
+    uint32_t below = 0;
+    const uint32_t x = tid < (int)blockIdx.x ? totals[tid] : 0u;  // <= 256 buckets <= kThreads
+    block_exclusive_scan(x, wsum, &below);
+    start = below;
+    cnt = totals[blockIdx.x];
+  }
+  for (int64_t base = 0; base < cnt; base += kTile) {
+    const int64_t nvalid = cnt - base < kTile ? cnt - base : kTile;
+    uint32_t key[kItems], val[kItems];
+    if constexpr (KS > 0) {
+      decode_tile_keys<KS>(rec, kend, base, n, sval, kend);  // sval: scratch until the scatter
+      __syncthreads();
+    }
+    // (loading the next tile's pairs ahead, over this tile's link stores, measured slower
+    // beside the executor: 6.31-6.35 against 6.09-6.10 ms per config 2 step)
+#pragma unroll
+    for (int it = 0; it < kItems; ++it) {
+      const int p = (wv * kItems + it) * 64 + lane;
+      const bool valid = p < nvalid;
+      const int64_t idx = start + base + p;
+      // pads sort last: both digits 63, after every real key of the tile (stable)
+      if constexpr (KS > 0) {
+        key[it] = valid ? sval[p] : 0xffffffffu;
+        val[it] = (uint32_t)idx;
+      } else {
+        key[it] = valid ? ld32<NT>(kin + idx) : 0xffffffffu;
+        val[it] = valid ? ld32<NT>(vin + idx) : 0u;
+      }
+    }
+    chain_sort_round(key, val, 0, skey, sval, wcnt, tstart, wsum);
+    if (low > kChainRB) {  // (uniform)
+#pragma unroll
+      for (int it = 0; it < kItems; ++it) {
+        const int p = (wv * kItems + it) * 64 + lane;
+        key[it] = skey[p];
+        val[it] = sval[p];
+      }
+      chain_sort_round(key, val, kChainRB, skey, sval, wcnt, tstart, wsum);
+    }
+    // the tile is sorted by player, each player's slots in time order
+    uint32_t is_last = 0u, has = 0u;  // bit k: element k of this thread ends a run / has a predecessor
+#pragma unroll 2
+    for (int k = 0; k < kItems; ++k) {
+      const int i = k * kThreads + tid;
+      if (i < nvalid) {
+        const uint32_t kk = skey[i];
+        if (kk < kend) {
+          const uint32_t v = sval[i];
+          const bool next = i + 1 < nvalid && skey[i + 1] == kk;
+          bool pred = i > 0 && skey[i - 1] == kk;
+          if (!pred) {  // first of its run: the player's last slot of an earlier tile links here
+            const uint32_t t = last_seen[kk & lmask];
+            if (t != kChainEmpty) {
+              pred = true;
+              const uint32_t ts = t & kMatchMask;
+              if (ts >= vlo && ts < vhi) link[ts] = v / (uint32_t)slots_per_match | (t & kLinkHasPred);
+            }
+          }
+          if (next) {
+            if (v >= vlo && v < vhi)  // this part's slot range (link_parts)
+              link[v] = sval[i + 1] / (uint32_t)slots_per_match | (pred ? kLinkHasPred : 0u);
+          } else {
+            is_last |= 1u << k;
+          }
+          if (pred) has |= 1u << k;
+        }
+      }
+    }
+    __syncthreads();  // every first has read T before the lasts replace its entries
+#pragma unroll 2
+    for (int k = 0; k < kItems; ++k) {
+      const int i = k * kThreads + tid;
+      if (is_last >> k & 1u) last_seen[skey[i] & lmask] = sval[i] | (has >> k & 1u ? kLinkHasPred : 0u);
+    }
+    __syncthreads();  // skey / sval are rewritten by the next tile
+  }
+  __syncthreads();
+  for (int e = tid; e <= (int)lmask; e += kThreads) {  // the last slot of every player seen
+    const uint32_t t = last_seen[e];
+    if (t != kChainEmpty) {
+      const uint32_t ts = t & kMatchMask;
+      if (ts >= vlo && ts < vhi) link[ts] = kNoMatch | (t & kLinkHasPred);
+    }
+  }
+}
+
 }  // namespace
 
 size_t radix_sort_workspace_bytes(int64_t n) {
@@ -561,13 +757,41 @@ int launch_radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, 
 template <int K, int RB, int NT>
 static void sched_sort_k(const int32_t* rec, int64_t n, uint32_t kend, int bits, uint32_t* ka,
                          uint32_t* va, uint32_t* kb, uint32_t* vb, uint32_t* counts,
-                         int64_t tiles, uint32_t* link, const SchedInit& init, hipStream_t s) {
+                         int64_t tiles, uint32_t* link, const SchedInit& init, bool chain,
+                         hipStream_t s) {
   constexpr int S = 2 * K;
   constexpr int kR = 1 << RB;
   uint32_t* totals = counts + tiles * kR;
   const dim3 grid((unsigned)tiles), block(kThreads);
   const uint32_t *ki = nullptr, *vi = nullptr;
   uint32_t *ko = kb, *vo = vb;
+  if (chain) {  // one partition by the bits above `low`, then one workgroup per bucket (sched_chain)
+    const int low = bits < kChainLowBits ? bits : kChainLowBits, top = bits - low;
+    const int parts = link_parts(n);
+    if (top > 0) {
+      // Players fill the buckets below nb.  The slots without state (key kend: 2 % of the
+      // matches of the bench stream, five buckets' worth) would all land in kend's bucket and
+      // make its workgroup the long pole, so the partition keys them with the first key of
+      // bucket nb instead, which no workgroup chains (when nb is a digit of its own, < 256).
+      const uint32_t nb = ((kend - 1u) >> low) + 1u;
+      const uint32_t knone = nb < (uint32_t)kR ? nb << low : kend;
+      hipLaunchKernelGGL((radix_upsweep<K, RB, NT>), grid, block, 0, s, nullptr, rec, kend, n, low, counts, tiles,
+                         init, knone);
+      hipLaunchKernelGGL(radix_rowscan, dim3(kR), block, 0, s, counts, tiles, totals);
+      hipLaunchKernelGGL((radix_downsweep<K, false, RB, NT>), grid, block, 0, s, nullptr, nullptr, rec, kend, ko,
+                         vo, n, low, counts, totals, tiles, S, nullptr, 0u, 0xffffffffu, 1, nullptr, 0, knone);
+      for (int q = 0; q < parts; ++q)
+        hipLaunchKernelGGL((sched_chain<0, NT>), dim3(nb), block, 0, s, ko, vo, nullptr, kend, n, low,
+                           totals, S, link, (uint32_t)(n * q / parts), (uint32_t)(n * (q + 1) / parts),
+                           n / S, SchedInit{});
+    } else {
+      for (int q = 0; q < parts; ++q)
+        hipLaunchKernelGGL((sched_chain<K, NT>), dim3(1), block, 0, s, nullptr, nullptr, rec, kend, n, low,
+                           nullptr, S, link, (uint32_t)(n * q / parts), (uint32_t)(n * (q + 1) / parts),
+                           n / S, q == 0 ? init : SchedInit{});
+    }
+    return;
+  }
   for (int shift = 0; shift < bits; shift += RB) {
     const bool first = shift == 0, last = shift + RB >= bits;
     // the last pass of a multi-pass sort over few digits (1M players: bits 16..19, 16
@@ -647,12 +871,26 @@ int launch_sched_sort(int K, const int32_t* rec, int64_t M, uint32_t num_players
   // sort_nt >= 0: the caller's choice (WindowPipeline: loads-only between DP merges)
   const int nt = nt_e ? atoi(nt_e) : sort_nt >= 0 ? sort_nt : 0;
   const bool wide = bits <= 20 && rb_env == 10;
+  // The chain pass (sched_chain) for rosters of <= 2^20 players; above that (config 5) the
+  // three LSD passes stay.  ANA_SCHED_CHAIN=1 / 0 forces it / the LSD passes; the
+  // ANA_SORT_RB=10 and ANA_SCHED_RUNS=0 experiments select the LSD passes they belong to.
+  // Unforced, the chain pass runs where its one workgroup per bucket is not the long pole.
+  // A workgroup chains a tile in ~26 us (0.79 ms for the 30 tiles of a config 2 bucket),
+  // the LSD passes take ~27 ps per slot (1.6 ms for 60M) on top of ~40 us of launches:
+  // the chain pass wins while a bucket averages under 2 tiles + n / 128 slots, i.e. with
+  // >= 128 buckets at any window size, or in small windows.  (The small-window end of this
+  // rule is reasoned from those two rates, not measured.)
+  const char* chain_e = getenv("ANA_SCHED_CHAIN");
+  const int top = bits > kChainLowBits ? bits - kChainLowBits : 0;
+  const bool chain_pays = (n >> top) <= 2 * kTile + n / 128;
+  const bool chain = (chain_e ? atoi(chain_e) != 0 : kChainDefault && chain_pays) && bits <= 20 && !wide &&
+                     local_runs();
   const bool known = with_team_size(K, [&](auto k) {
     constexpr int kK = decltype(k)::value;
-    if (wide) sched_sort_k<kK, 10, 0>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s);
-    else if (nt == 1) sched_sort_k<kK, 8, 1>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s);
-    else if (nt == 2) sched_sort_k<kK, 8, 2>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s);
-    else sched_sort_k<kK, 8, 0>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, s);
+    if (wide) sched_sort_k<kK, 10, 0>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, chain, s);
+    else if (nt == 1) sched_sort_k<kK, 8, 1>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, chain, s);
+    else if (nt == 2) sched_sort_k<kK, 8, 2>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, chain, s);
+    else sched_sort_k<kK, 8, 0>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, chain, s);
   });
   return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
