@@ -28,7 +28,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 HIP_SOURCES = ["kernels.hip", "radix_sort.hip", "dataflow.hip", "sweep.hip", "telemetry.hip", "levels.hip",
-               "digest.hip", "select.hip", "ladder.hip", "matchmake.hip", "career.hip"]
+               "digest.hip", "select.hip", "ladder.hip", "matchmake.hip", "career.hip", "score.hip"]
 # per-file device flags.  The executor's divisions/sqrt take the 1-ulp hardware
 # paths (v_rcp_f32 instead of the ~10-instruction IEEE division expansion: -9%
 # static instructions); NaN/Inf semantics are untouched (no -ffinite-math-only),
@@ -40,6 +40,8 @@ HIP_FLAGS = {n: ["-fapprox-func", "-freciprocal-math", "-fno-signed-zeros"]
 HIP_FLAGS["matchmake.hip"] = ["-ffp-contract=off"]
 # a career's score is the one IEEE subtraction the host mirror does (csrc/career_core.h)
 HIP_FLAGS["career.hip"] = ["-ffp-contract=off"]
+# the scorecard's d and sum sigma^2 are the sums the preview kernel forms (csrc/score.hip)
+HIP_FLAGS["score.hip"] = ["-ffp-contract=off"]
 CPP_SOURCES = ["host.cpp", "ingest.cpp", "batch_host.cpp", "telemetry_file.cpp", "bindings.cpp"]
 
 

@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "ladder_core.h"
 #include "matchmake_core.h"
+#include "score_core.h"
 #include "select_core.h"
 
 namespace {
@@ -949,6 +950,115 @@ void careers_add(Tensor table, Tensor rec, Tensor rows, int64_t base, int64_t P,
             "career_fold");
 }
 
+// K14 (score.hip; host mirrors host.cpp): the operands both calls share -- rec [M, 2K+2] and its
+// packed rows [M, W] on dev, aligned for the device's vector loads -> M
+int64_t check_window(const Tensor& rec, const Tensor& rows, int64_t K, const torch::Device& dev, const char* what) {
+  const int64_t M = check_rec(rec, K, dev, what);
+  check(rows, "rows", torch::kFloat32, dev);
+  TORCH_CHECK(rows.dim() == 2 && rows.size(0) == M && rows.size(1) >= 10 * K + 2 && rows.size(1) % 4 == 0, what,
+              ": rows must be the packed [M, W] output rows of rec's matches");
+  TORCH_CHECK(M * 2 * K <= ana::kMaxSlots, what, ": a window holds at most ", ana::kMaxSlots, " slots");
+  if (dev.is_cuda())
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(rec.data_ptr()) % (K % 2 == 0 ? 8 : 16) == 0 &&
+                    reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0,
+                what, ": rec and rows must be 16-B aligned");
+  return M;
+}
+
+// priors [M, 4 * 2K] fp32 (field-major: shared mu, sigma, mode mu, sigma) of one window against
+// the chain table [P, 16] (mu, sigma per granule), which is advanced in place to the state
+// after the window (score_core.h).  The device path is six stream-ordered steps (keys, sort,
+// summaries, stitch, apply, fields) without a host read.
+Tensor priors_add(Tensor chain, Tensor rec, Tensor rows) {
+  const auto dev = chain.device();
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "priors_add: rec must be [M, 2K+2]");
+  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t M = check_window(rec, rows, K, dev, "priors_add");
+  TORCH_CHECK(chain.dim() == 2, "priors_add: chain must be [P, 16]");
+  const int64_t P = chain.size(0);
+  TORCH_CHECK(P <= 0x7fffffffLL, "priors_add: P must fit in int32");
+  check_rows(chain, "chain", P, ana::kBaseFloats, dev);
+  Tensor priors = torch::empty({M, 8 * K}, chain.options());
+  if (M == 0) return priors;
+  if (!dev.is_cuda()) {
+    TORCH_CHECK(ana::host_priors_add((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                     chain.data_ptr<float>(), priors.data_ptr<float>()) == 0,
+                "priors_add: bad arguments");
+    return priors;
+  }
+  const hipStream_t s = stream_of(chain);
+  const int64_t n = M * 2 * K;
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
+  Tensor keys = torch::empty({n}, i32), vals = torch::empty({n}, i32);
+  Tensor events = torch::empty({n, (int64_t)ana::kPriorEventWords}, i32);
+  Tensor slot_priors = torch::empty({n, 4}, i32);  // the prior words slot-major, 16 B per slot
+  check_hip(ana::launch_prior_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                   u32p(keys), u32p(vals), u32p(events), u32p(slot_priors), s),
+            "prior_keys");
+  int bits = 1;
+  while ((P >> bits) != 0) ++bits;  // bit_length(P): the key P of a slot that is not live sorts last
+  const auto sorted = P > 0 ? sort_pairs_on_stream(keys, vals, n, bits, s) : std::vector<Tensor>{keys, vals};
+  Tensor edges = torch::empty({(int64_t)ana::prior_edge_bytes(n)}, i32.dtype(torch::kUInt8));
+  check_hip(ana::launch_prior_scan(u32p(sorted[0]), u32p(sorted[1]), u32p(events), n, (int)K, P,
+                                   chain.data_ptr<float>(), edges.data_ptr<uint8_t>(), u32p(slot_priors),
+                                   priors.data_ptr<float>(), s),
+            "prior_scan");
+  return priors;
+}
+
+// adds the predictions of one window's priors to the scorecard table [6, 33, 4] int64 in
+// place; returns the pred rows [M, 4] int32 (flags word, p_win0 bits, p_outcome bits, 0) when
+// ``keep``, else an empty tensor
+Tensor score_add(Tensor table, Tensor rec, Tensor priors, Tensor rows, c10::optional<Tensor> attrs, Tensor vst,
+                 int64_t P, double beta2, double unknown_sigma, int64_t track, int64_t modes, bool keep) {
+  const auto dev = table.device();
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "score_add: rec must be [M, 2K+2]");
+  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t M = check_window(rec, rows, K, dev, "score_add");
+  check(table, "table", torch::kInt64, dev);
+  TORCH_CHECK(table.numel() == ana::kScoreTableWords, "score_add: table must be [6, 33, 4]");
+  check_rows(priors, "priors", M, 8 * K, dev);
+  check_vst(vst, dev, "score_add");
+  TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "score_add: P must fit in int32");
+  const float* at = nullptr;
+  if (attrs.has_value() && attrs->defined()) at = check_attrs(*attrs, P, dev, "score_add");
+  TORCH_CHECK(track == ana::kScoreShared || track == ana::kScoreMode, "score_add: unknown track ", track);
+  TORCH_CHECK(modes >= 0 && (modes & ~(int64_t)ana::kScoreAllModes) == 0,
+              "score_add: the modes mask must name modes 0..5");
+  Tensor pred = torch::empty({keep ? M : 0, (int64_t)ana::kPredWords}, rec.options());
+  if (M == 0) return pred;
+  int32_t* pp = keep ? pred.data_ptr<int32_t>() : nullptr;
+  if (!dev.is_cuda()) {
+    TORCH_CHECK(ana::host_score_add((int)K, rec.data_ptr<int32_t>(), priors.data_ptr<float>(), rows.data_ptr<float>(),
+                                    rows.size(1), M, at, vst.data_ptr<float>(), P, (float)beta2, (float)unknown_sigma,
+                                    (int)track, (uint32_t)modes, table.data_ptr<int64_t>(), pp) == 0,
+                "score_add: bad arguments");
+    return pred;
+  }
+  check_hip(ana::launch_score((int)K, rec.data_ptr<int32_t>(), priors.data_ptr<float>(), rows.data_ptr<float>(),
+                              rows.size(1), M, at, vst.data_ptr<float>(), P, (float)beta2, (float)unknown_sigma,
+                              (int)track, (uint32_t)modes, table.data_ptr<int64_t>(), pp, stream_of(table)),
+            "score");
+  return pred;
+}
+
+// nlog2_q20 (score_core.h) of fp32 bit patterns [n] int32 -> [n] int64, computed where the
+// tensor lives: the one function, compiled for the host and for the device
+Tensor nlog2_q20(Tensor bits) {
+  const auto dev = bits.device();
+  check(bits, "bits", torch::kInt32, dev);
+  const int64_t n = bits.numel();
+  Tensor out = torch::empty({n}, bits.options().dtype(torch::kInt64));
+  if (n == 0) return out;
+  if (dev.is_cuda()) {
+    check_hip(ana::launch_nlog2_q20(u32p(bits), n, out.data_ptr<int64_t>(), stream_of(bits)), "nlog2_q20");
+  } else {
+    const int32_t* b = bits.data_ptr<int32_t>();
+    for (int64_t i = 0; i < n; ++i) out.data_ptr<int64_t>()[i] = ana::nlog2_q20((uint32_t)b[i]);
+  }
+  return out;
+}
+
 // K11 (ladder.hip; host mirror host.cpp host_ladder): the ladders of the tracks of ``mask``
 // (bit t = granule t) of a roster's state [P, 32], as [order, score, rank] per track in
 // ascending track order: order int32 [R] (best first), score fp32 [R], rank int32 [P]
@@ -1214,6 +1324,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "career table [P, 16] int32 in place: careers_add(table, rec, rows, base, P, track, score, modes)");
   m.attr("CAREER_WORDS") = ana::kCareerWords;
   m.attr("CAREER_TILE") = ana::kCareerTile;
+  m.def("priors_add", &priors_add, "K14: the pre-match priors [M, 4 * 2K] fp32 of one window (rec [M, 2K+2] joined with "
+        "its packed rows [M, W]) against the chain table [P, 16], advanced in place: priors_add(chain, rec, rows)");
+  m.def("score_add", &score_add, "K14: add the predictions of a window's priors to the scorecard table [6, 33, 4] int64 "
+        "in place; returns the pred rows [M, 4] int32 when keep: score_add(table, rec, priors, rows, attrs, vst, P, "
+        "beta2, unknown_sigma, track, modes, keep)",
+        py::arg("table"), py::arg("rec"), py::arg("priors"), py::arg("rows"), py::arg("attrs"), py::arg("vst"),
+        py::arg("P"), py::arg("beta2"), py::arg("unknown_sigma"), py::arg("track"), py::arg("modes"), py::arg("keep"));
+  m.def("nlog2_q20", &nlog2_q20, "K14: -log2(p) * 2^20 of fp32 bit patterns [n] int32 -> [n] int64, integer operations only");
+  m.attr("SCORE_BINS") = ana::kScoreBins;
+  m.attr("PRIOR_TILE") = ana::kPriorTile;
+  m.attr("NLOG2_CAP") = (int64_t)ana::kNlog2Cap;
   m.attr("MAX_SLOTS") = (int64_t)ana::kMaxSlots;
   m.attr("LADDER_CONSERVATIVE") = (int)ana::kLadderConservative;
   m.attr("LADDER_MU") = (int)ana::kLadderMu;

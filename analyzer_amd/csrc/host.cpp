@@ -17,6 +17,7 @@
 #include "ladder_core.h"
 #include "matchmake_core.h"
 #include "rate_core.h"
+#include "score_core.h"
 #include "select_core.h"
 
 namespace ana {
@@ -418,51 +419,68 @@ int64_t host_ladder(const float* state, int64_t P, int track, int score, float m
   return R;
 }
 
-// K12: the device's preview per record, on rate_k's own code path (decode_record, the prior
-// loop in slot order, copy_dup_priors, match_quality) in fp64, so status and quality are the
-// bits host_rate writes; p_win0 from the same sums
+// K12 / K14: what `rate` would make of one record against stored (mu, sigma) pairs, on
+// rate_k's own code path (decode_record, the prior loop in slot order, copy_dup_priors,
+// match_quality) in fp64, so status and quality are the bits host_rate writes.  raw(j, x) gives
+// slot j's stored shared (mu, sigma) and mode-track (mu, sigma).  d and den are the sums
+// p_win0 = win_probability(d, den) is made of, on the mode track or (shared) the shared one.
+template <int K, class Raw>
+static void preview_match(const int32_t* r, int64_t P, Raw&& raw, const float* attrs, const float* vst, double beta2,
+                          double us, bool shared, MatchWork<double, K>& w, double& q, double& d, double& den) {
+  constexpr int S = 2 * K;
+  const float no_attr[4] = {NAN, NAN, NAN, 0.f};
+  decode_record<double, K>(r, P, w);
+  q = d = den = 0;
+  if (w.status != kRated) return;
+  uint8_t st = kRated;
+  uint32_t nulls = 0;
+  for (int j = 0; j < S && st == kRated; ++j) {
+    if (w.first[j] != j) continue;
+    double x[4];
+    raw(j, x);
+    st = make_prior<double, K>(w, j, x[0], x[1], x[2], x[3], attrs ? attrs + (int64_t)w.id[j] * 4 : no_attr, us, vst,
+                               nulls);
+  }
+  w.status = st;
+  if (st != kRated) return;
+  copy_dup_priors<double, K>(w);
+  if (w.n0 == 0 || w.n1 == 0) {
+    w.status = kErrEmptyRoster;
+    return;
+  }
+  q = match_quality<double, K>(w.mm, w.sm, w.n0, w.n1, beta2);
+  double s2 = 0;
+  bool finite = true;
+  for (int j = 0; j < S; ++j) {
+    const bool in0 = j < K && j < w.n0, in1 = j >= K && j - K < w.n1;
+    if (!(in0 || in1)) continue;
+    const double mu = shared ? w.ms[j] : w.mm[j], sg = shared ? w.ss[j] : w.sm[j];
+    s2 += sg * sg;
+    d += in0 ? mu : -mu;
+    finite = finite && prior_finite<double>(w.ms[j], w.ss[j], w.mm[j], w.sm[j]);
+  }
+  den = (double)(w.n0 + w.n1) * beta2 + s2;
+  if (!finite || !isfinite(q) || !isfinite(win_probability<double>(d, den))) w.status = kErrNumeric;
+}
+
 template <int K>
 static void preview_k(const int32_t* rec, int64_t M, const float* state, const float* attrs, const float* vst,
                       int64_t P, double beta2, double us, int32_t* out) {
   constexpr int S = 2 * K;
-  const float no_attr[4] = {NAN, NAN, NAN, 0.f};
   for (int64_t m = 0; m < M; ++m) {
     MatchWork<double, K> w;
-    decode_record<double, K>(rec + m * (S + 2), P, w);
-    double q = 0, pw = 0;
-    if (w.status == kRated) {
-      uint8_t st = kRated;
-      uint32_t nulls = 0;
-      for (int j = 0; j < S && st == kRated; ++j) {
-        if (w.first[j] != j) continue;
-        const float* row = state + (int64_t)w.id[j] * kRowFloats;
-        const float* gm = row + 4 * (1 + w.mode);
-        st = make_prior<double, K>(w, j, (double)row[0], (double)row[2], (double)gm[0], (double)gm[2],
-                                   attrs ? attrs + (int64_t)w.id[j] * 4 : no_attr, us, vst, nulls);
-      }
-      w.status = st;
-      if (st == kRated) {
-        copy_dup_priors<double, K>(w);
-        if (w.n0 == 0 || w.n1 == 0) {
-          w.status = kErrEmptyRoster;
-        } else {
-          q = match_quality<double, K>(w.mm, w.sm, w.n0, w.n1, beta2);
-          double s2 = 0, d = 0;
-          bool finite = true;
-          for (int j = 0; j < S; ++j) {
-            const bool in0 = j < K && j < w.n0, in1 = j >= K && j - K < w.n1;
-            if (!(in0 || in1)) continue;
-            s2 += w.sm[j] * w.sm[j];
-            d += in0 ? w.mm[j] : -w.mm[j];
-            finite = finite && prior_finite<double>(w.ms[j], w.ss[j], w.mm[j], w.sm[j]);
-          }
-          pw = win_probability<double>(d, (double)(w.n0 + w.n1) * beta2 + s2);
-          if (!finite || !isfinite(q) || !isfinite(pw)) w.status = kErrNumeric;
-        }
-      }
-    }
+    double q, d, den;
+    preview_match<K>(
+        rec + m * (S + 2), P,
+        [&](int j, double* x) {
+          const float* row = state + (int64_t)w.id[j] * kRowFloats;
+          const float* gm = row + 4 * (1 + w.mode);
+          x[0] = row[0], x[1] = row[2], x[2] = gm[0], x[3] = gm[2];
+        },
+        attrs, vst, beta2, us, false, w, q, d, den);
     const bool rated = w.status == kRated, afkish = w.status == kAfk || w.status == kInvalidRosters;
-    const float qo = rated ? (float)q : afkish ? 0.f : NAN, po = rated ? (float)pw : NAN;
+    const float qo = rated ? (float)q : afkish ? 0.f : NAN;
+    const float po = rated ? (float)win_probability<double>(d, den) : NAN;
     int32_t* o = out + m * kPreviewWords;
     o[0] = (int32_t)w.status;
     o[1] = (int32_t)ladder_bits(qo);
@@ -477,6 +495,89 @@ int host_preview(int K, const int32_t* rec, int64_t M, const float* state, const
   const bool known = with_team_size(
       K, [&](auto k) { preview_k<decltype(k)::value>(rec, M, state, attrs, vst, P, beta2, unknown_sigma, out); });
   return known ? 0 : -1;
+}
+
+// K14: the chain walked in match order; every slot of a match reads before any of them writes
+template <int K>
+static void priors_add_k(const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, float* chain,
+                         float* priors) {
+  constexpr int S = 2 * K;
+  uint32_t* ch = reinterpret_cast<uint32_t*>(chain);
+  uint32_t* out = reinterpret_cast<uint32_t*>(priors);
+  for (int64_t m = 0; m < M; ++m) {
+    const int32_t* r = rec + m * (S + 2);
+    const uint32_t live = prior_live_mask<K>(r, P);
+    const int mode = meta_mode((uint32_t)r[S]);
+    uint32_t* pr = out + m * (4 * S);
+    for (int j = 0; j < S; ++j) {
+      uint32_t w[4] = {kPriorNull, kPriorNull, kPriorNull, kPriorNull};
+      if ((live >> j) & 1u) prior_pick(prior_from_chain(ch + (int64_t)r[j] * kBaseFloats), mode, w);
+      for (int f = 0; f < 4; ++f) pr[f * S + j] = w[f];
+    }
+    if (!live) continue;  // the row is only read for a live slot
+    uint32_t row[5 * S + 2];
+    memcpy(row, rows + m * W, sizeof(row));
+    if (select_row_status<K>(row) != kRated) continue;
+    const uint32_t writes = prior_last_mask<K>(r, live);
+    for (int j = 0; j < S; ++j) {
+      if (!((writes >> j) & 1u)) continue;
+      uint32_t* c = ch + (int64_t)r[j] * kBaseFloats;
+      const PriorState s = prior_combine(prior_from_chain(c),
+                                         prior_write(mode, row[j], row[S + j], row[3 * S + j], row[4 * S + j]));
+      for (int i = 0; i < 2 * kTracks; ++i) c[i] = s.w[i];
+    }
+  }
+}
+
+int host_priors_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, float* chain,
+                    float* priors) {
+  if (W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll) return -1;
+  return with_team_size(K, [&](auto k) { priors_add_k<decltype(k)::value>(rec, rows, W, M, P, chain, priors); })
+             ? 0 : -1;
+}
+
+// K14: the prediction of every match from its priors, on preview's fp64 path, and its score
+template <int K>
+static void score_add_k(const int32_t* rec, const float* priors, const float* rows, int64_t W, int64_t M,
+                        const float* attrs, const float* vst, int64_t P, double beta2, double us, int track,
+                        uint32_t modes, int64_t* table, int32_t* pred) {
+  constexpr int S = 2 * K;
+  for (int64_t m = 0; m < M; ++m) {
+    const int32_t* r = rec + m * (S + 2);
+    const float* pr = priors + m * (4 * S);
+    MatchWork<double, K> w;
+    double q, d, den;
+    preview_match<K>(
+        r, P, [&](int j, double* x) { x[0] = pr[j], x[1] = pr[S + j], x[2] = pr[2 * S + j], x[3] = pr[3 * S + j]; },
+        attrs, vst, beta2, us, track == kScoreShared, w, q, d, den);
+    const uint32_t meta1 = (uint32_t)r[S + 1];
+    const bool rated = w.status == kRated, w0 = meta_winner0(meta1), w1 = meta_winner1(meta1);
+    const float pw = rated ? (float)win_probability<double>(d, den) : NAN;
+    const float po = rated && w0 != w1 ? (float)win_probability<double>(w0 ? d : -d, den) : NAN;
+    uint32_t row[5 * S + 2];
+    memcpy(row, rows + m * W, sizeof(row));
+    const uint32_t word = score_match(select_row_status<K>(row), (uint32_t)r[S], meta1, modes, w.status, pw, po,
+                                      [&](int c, int64_t x) { table[c] += x; });
+    if (pred != nullptr) {
+      int32_t* o = pred + m * kPredWords;
+      o[0] = (int32_t)word;
+      o[1] = (int32_t)ladder_bits(pw);
+      o[2] = (int32_t)ladder_bits(po);
+      o[3] = 0;
+    }
+  }
+}
+
+int host_score_add(int K, const int32_t* rec, const float* priors, const float* rows, int64_t W, int64_t M,
+                   const float* attrs, const float* vst, int64_t P, float beta2, float unknown_sigma, int track,
+                   uint32_t modes, int64_t* table, int32_t* pred) {
+  if (W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll || (track != kScoreShared && track != kScoreMode) ||
+      (modes & ~kScoreAllModes))
+    return -1;
+  return with_team_size(K, [&](auto k) {
+    score_add_k<decltype(k)::value>(rec, priors, rows, W, M, attrs, vst, P, beta2, unknown_sigma, track, modes, table,
+                                    pred);
+  }) ? 0 : -1;
 }
 
 // fp32 player_prior of one player, as the device's load_prior

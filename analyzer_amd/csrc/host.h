@@ -65,6 +65,16 @@ int64_t host_ladder(const float* state, int64_t P, int track, int score, float m
 // -1: bad arguments.
 int host_careers_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base, int64_t P,
                      int track, int score, uint32_t modes, int32_t* table);
+// K14 host mirror (score_core.h).  priors_add: the priors [M][4 * 2K] of rec [M][2K+2] joined with
+// rows [M][W], walking chain [P][kBaseFloats] in match order and leaving it after the window,
+// bit-identical to the device.  score_add: the prediction of every match from its priors on
+// preview's fp64 path (so status and p_win0 are host_preview's bits) added into table
+// [kModes][kScoreBins + 1][4]; pred (nullable) [M][kPredWords]; attrs may be null.  -1: bad arguments.
+int host_priors_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, float* chain,
+                    float* priors);
+int host_score_add(int K, const int32_t* rec, const float* priors, const float* rows, int64_t W, int64_t M,
+                   const float* attrs, const float* vst, int64_t P, float beta2, float unknown_sigma, int track,
+                   uint32_t modes, int64_t* table, int32_t* pred);
 // K12 host mirror (matchmake_core.h); out / records as launch_preview / launch_balance /
 // launch_queue_keys (kernels.h) lay them out; attrs may be null.  preview runs rate's own
 // fp64 path (status and quality are the bits host_rate writes); balance chooses the split in

@@ -99,6 +99,32 @@ int launch_career_keys(int K, const int32_t* rec, const float* rows, int64_t W, 
 int launch_career_fold(const uint32_t* keys, const uint32_t* vals, const uint32_t* events, int64_t n, int K,
                        int64_t base, int64_t P, int32_t* table, void* edges, hipStream_t s);
 
+// K14 scorecard (score.hip, score_core.h).  Priors: one window rec [M][2K+2] joined with its
+// packed rows [M][W] (alignment as for K10), M * 2K <= kMaxSlots; chain [P][kBaseFloats] is read
+// and advanced in place; priors [M][4 * 2K] (field-major: shared mu, sigma, mode mu, sigma; 16-B
+// aligned).  prior_keys writes per slot i = m * 2K + j the sort key (the player of a live slot,
+// else P), the value (i | mode << 28 | write flag << 31), the 16-B event of a writing slot
+// (events: 4 words per slot, 16-B aligned) and, into slot_priors (4 words per slot, 16-B
+// aligned), the NaN priors of the slots that are not live; the pairs are sorted with
+// launch_radix_sort_pairs on bit_length(P) bits; prior_scan takes the sorted pairs [n = M * 2K]
+// (P = 0: unsorted will do), adds the prior words of the live slots to slot_priors, lays all of
+// them out by field in priors and leaves chain after the window (edges: prior_edge_bytes(n)
+// bytes, 16-B aligned).  Everything is stream-ordered.
+constexpr int kPriorTile = 4096;  // sorted elements per workgroup of the scan
+size_t prior_edge_bytes(int64_t n);
+int launch_prior_keys(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t* keys,
+                      uint32_t* vals, uint32_t* events, uint32_t* slot_priors, hipStream_t s);
+int launch_prior_scan(const uint32_t* keys, const uint32_t* vals, const uint32_t* events, int64_t n, int K, int64_t P,
+                      float* chain, void* edges, uint32_t* slot_priors, float* priors, hipStream_t s);
+// score: per match the prediction its priors make (attrs [P][4] 16-B aligned or null, vst:
+// kVstTiers floats; track: ScoreTrack; modes: bit per mode) added into table
+// [kModes][kScoreBins + 1][4] int64; pred (nullable, 16-B aligned): [M][kPredWords] int32
+int launch_score(int K, const int32_t* rec, const float* priors, const float* rows, int64_t W, int64_t M,
+                 const float* attrs, const float* vst, int64_t P, float beta2, float unknown_sigma, int track,
+                 uint32_t modes, int64_t* table, int32_t* pred, hipStream_t s);
+// out[i] = nlog2_q20(bits[i]) (score_core.h), i < n
+int launch_nlog2_q20(const uint32_t* bits, int64_t n, int64_t* out, hipStream_t s);
+
 // Stable LSD radix sort of (key, value) pairs on the low ``bits`` key bits
 // (radix_sort.hip).  Ping-pongs between the two buffer pairs; *result_in_alt
 // says which holds the result.  ws: radix_sort_workspace_bytes(n) bytes.

@@ -1,0 +1,547 @@
+// K14 scorecard: the belief before every match of a window, reconstructed from the match
+// stream rec [M][2K+2] joined with its packed output rows [M][W], and the score of the
+// prediction that belief makes (score_core.h).
+//
+// Priors.  chain [P][kBaseFloats] is updated in place, window by window; every value is a
+// copied bit pattern and prior_combine is associative, so priors and chain are the same bits
+// for any grid, tile size or cut of the history into calls.  No atomics, and no workgroup
+// waits on another: six stream-ordered steps.
+//
+//   keys       one lane per match: per slot the sort key -- the player of a live slot, else
+//              P --, the value (slot index | mode << 28 | write flag << 31) and, for a slot
+//              that writes, its 16-B event (s_mu, s_sig, m_mu, m_sig), so the later passes
+//              never touch the 128-B row line.  Slots that are not live get their NaN priors
+//              here (slot-major, 16 B per slot), and sort last.
+//   sort       launch_radix_sort_pairs on bit_length(P) bits: stable, so each player's slots
+//              come out in (match, slot) order.
+//   summaries  one workgroup per tile of kPriorTile sorted elements.  The exclusive scan is
+//              run as an inclusive scan of shifted terms: element i contributes the write of
+//              element i - 1 of the same key, so the scanned value is the state before i and
+//              one 16-B gather per element feeds it.  The runs of the tile's first and last
+//              key, the only ones that can go on in a neighbour tile, leave their totals
+//              (without any starting state) in edges[2 * tile + 0 / 1].
+//   stitch     one workgroup: the same scan over the 2 * tiles edges in tile order.  The
+//              first edge of a key contributes the key's chain row, so carry[e] is the state
+//              before edge e's stretch, starting state included; the last edge of a key
+//              stores the state after the window into the chain row.
+//   apply      the summaries scan again, now seeded: the first element of a key in the tile
+//              contributes carry[2 * tile] (the tile's first key), carry[2 * tile + 1] (its
+//              last key) or, for a run strictly inside the tile, the key's chain row.  Every
+//              live element stores the four prior words of its mode as one 16-B slot-major
+//              entry; the last element of an inner run stores the run's final state into
+//              its chain row.
+//   fields     one lane per match: the slot-major entries [M][2K][4] to the field-major
+//              priors [M][4][2K], 16-B loads and stores (four scattered 4-B stores per slot
+//              in apply instead cost more than this pass and its buffer).
+//
+// The table in place, without a race.  A key's chain row has one reader, the globally first
+// element of the key, and one writer, the globally last, and the written value depends on the
+// read one through the scan.  A run inside one tile that is neither the tile's first nor last
+// key is read and written by that tile's apply workgroup alone: the first element's lane
+// loads the row, the scan (shuffles, LDS, barriers) carries it to the last element's lane,
+// which stores; no other workgroup sees the key.  Every other run -- across tiles or touching
+// a tile's end -- is in the edges, and its row is read and written by the stitch workgroup
+// alone, first edge to last edge through the same scan; apply never touches that row and
+// takes the starting state from carry, which stitch filled before it overwrote the row.
+//
+// Score.  One lane per match over rec, priors, the row's status byte and (behind a NULL
+// shared track only) attrs: player_prior per slot, then d and sum sigma^2 in preview_kernel's
+// operation order (matchmake.hip; the butterfly as butterfly_sum), p_win0 and p_outcome.  The
+// table is integer sums only: each workgroup adds into a copy in LDS and then once per
+// non-zero cell into the global table, so any order gives the same bits.
+//
+// Built with -ffp-contract=off: every fp32 operation is the one written.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "common.h"
+#include "kernels.h"
+#include "record_dev.h"
+#include "score_core.h"
+
+namespace ana {
+
+namespace {
+
+constexpr int kPriorThreads = 256;
+constexpr int kPriorWaves = kPriorThreads / 64;
+constexpr int kPriorIters = kPriorTile / kPriorThreads;
+static_assert(kPriorTile % kPriorThreads == 0, "a tile is a whole number of iterations");
+constexpr uint32_t kNoKey = 0xffffffffu;  // above every sort key (keys are <= P < 2^31)
+// an edge or a carry: [key, mask, w[14]], 64 B
+constexpr int kEdgeWords = 16;
+static_assert(sizeof(PriorState) == 4 * (kEdgeWords - 1), "an edge holds a key and a state");
+constexpr int kScoreThreads = 256;
+
+typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+template <int K>
+__global__ void __launch_bounds__(kPriorThreads) prior_keys_kernel(
+    const int32_t* __restrict__ rec, const uint32_t* __restrict__ rows, int64_t W, int64_t M, int64_t P,
+    uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, v4u* __restrict__ events,
+    v4u* __restrict__ slot_priors) {
+  constexpr int S = 2 * K;
+  const int64_t m = (int64_t)blockIdx.x * kPriorThreads + threadIdx.x;
+  if (m >= M) return;
+  int32_t r[S + 2];
+  load_record<K>(rec, m, r);
+  const uint32_t live = prior_live_mask<K>(r, P);
+  const uint32_t mode = (uint32_t)meta_mode((uint32_t)r[S]);
+  uint32_t writes = 0u;
+  uint32_t sh[2 * S], md[2 * S];  // the fields (s_mu, s_sig) and (m_mu, m_sig), as 8-B loads
+  if (live) {
+    const uint32_t* row = rows + m * W;
+    const v2u tail = *reinterpret_cast<const v2u*>(row + 5 * S);
+    if ((tail[1] & 0xffu) == kRated) {
+      writes = prior_last_mask<K>(r, live);
+      const v2u* a = reinterpret_cast<const v2u*>(row);
+      const v2u* b = reinterpret_cast<const v2u*>(row + 3 * S);
+#pragma unroll
+      for (int c = 0; c < S; ++c) {
+        const v2u x = a[c], y = b[c];
+        sh[2 * c] = x[0];
+        sh[2 * c + 1] = x[1];
+        md[2 * c] = y[0];
+        md[2 * c + 1] = y[1];
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < S; ++j) {
+    const int64_t i = m * S + j;
+    const bool lv = (live >> j) & 1u, wr = (writes >> j) & 1u;
+    keys[i] = lv ? (uint32_t)r[j] : (uint32_t)P;
+    vals[i] = (uint32_t)i | (lv ? mode << kPriorModeShift : 0u) | (wr ? kPriorWriteBit : 0u);
+    if (wr) {
+      v4u e;
+      e[0] = sh[j];
+      e[1] = sh[S + j];
+      e[2] = md[j];
+      e[3] = md[S + j];
+      events[i] = e;
+    }
+    if (!lv) {
+      v4u none;
+      none[0] = none[1] = none[2] = none[3] = kPriorNull;
+      slot_priors[i] = none;
+    }
+  }
+}
+
+__device__ __forceinline__ PriorState shfl_up_state(const PriorState& a, int o) {
+  PriorState c;
+  c.mask = __shfl_up(a.mask, o, 64);
+#pragma unroll
+  for (int i = 0; i < 2 * kTracks; ++i) c.w[i] = __shfl_up(a.w[i], o, 64);
+  return c;
+}
+
+// word by word, so a state stays in registers on either side
+__device__ __forceinline__ void state_store(uint32_t* dst, const PriorState& a) {
+  dst[0] = a.mask;
+#pragma unroll
+  for (int i = 0; i < 2 * kTracks; ++i) dst[1 + i] = a.w[i];
+}
+__device__ __forceinline__ PriorState state_load(const uint32_t* src) {
+  PriorState c;
+  c.mask = src[0];
+#pragma unroll
+  for (int i = 0; i < 2 * kTracks; ++i) c.w[i] = src[1 + i];
+  return c;
+}
+
+// LDS of the workgroup scan, double-buffered over the iterations (one barrier each):
+// entry 0 is the carry of the earlier iterations, entry 1 + w the total of wave w
+struct ScanLds {
+  uint32_t key[2][kPriorWaves + 1];
+  uint32_t st[2][kPriorWaves + 1][kEdgeWords - 1];
+};
+
+__device__ __forceinline__ void scan_init(ScanLds& lds) {
+  if (threadIdx.x == 0) lds.key[0][0] = kNoKey;
+}
+
+// Iteration ``it`` of a segmented inclusive scan over terms in ascending key order, one per
+// lane: on return ``s`` covers the terms of the lane's key from the first one this workgroup
+// saw up to the lane's.  Lanes past the end pass kNoKey.
+__device__ __forceinline__ void scan_step(ScanLds& lds, int it, uint32_t key, PriorState& s) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = it & 1;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t ok = __shfl_up(key, o, 64);
+    const PriorState os = shfl_up_state(s, o);
+    if (lane >= o && ok == key) s = prior_combine(os, s);
+  }
+  if (lane == 63) {
+    lds.key[b][1 + wave] = key;
+    state_store(lds.st[b][1 + wave], s);
+  }
+  __syncthreads();
+  // keys ascend, so the entries that match are the last ones before this wave
+  PriorState before = prior_none();
+#pragma unroll
+  for (int e = 0; e < kPriorWaves; ++e)
+    if (e <= wave && lds.key[b][e] == key) before = prior_combine(before, state_load(lds.st[b][e]));
+  s = prior_combine(before, s);
+  if (t == kPriorThreads - 1) {  // read after the next barrier, written after this one
+    lds.key[b ^ 1][0] = key;
+    state_store(lds.st[b ^ 1][0], s);
+  }
+}
+
+// the write of the slot with sort value v (prior_none() when it does not write)
+__device__ __forceinline__ PriorState slot_write(uint32_t v, const v4u* __restrict__ events, int64_t n) {
+  const uint32_t slot = v & kPriorSlotMask;
+  if (!(v & kPriorWriteBit) || (int64_t)slot >= n) return prior_none();  // slot < n always: a permutation
+  const v4u e = events[slot];
+  return prior_write((int)((v >> kPriorModeShift) & 7u), e[0], e[1], e[2], e[3]);
+}
+
+__device__ __forceinline__ void chain_store(uint32_t* __restrict__ chain, uint32_t key, const PriorState& s) {
+  uint32_t* row = chain + (int64_t)key * kBaseFloats;
+#pragma unroll
+  for (int i = 0; i < 2 * kTracks; ++i) row[i] = s.w[i];
+}
+
+__device__ __forceinline__ void edge_store(uint32_t* __restrict__ edges, int64_t e, uint32_t key, const PriorState& s) {
+  edges[e * kEdgeWords] = key;
+  state_store(edges + e * kEdgeWords + 1, s);
+}
+
+// summaries (APPLY = false) and apply (APPLY = true) over one tile of the sorted pairs
+template <bool APPLY>
+__global__ void __launch_bounds__(kPriorThreads) prior_tile_kernel(
+    const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, const v4u* __restrict__ events, int64_t n,
+    uint32_t P, uint32_t* __restrict__ chain, uint32_t* __restrict__ edges,
+    const uint32_t* __restrict__ carry, v4u* __restrict__ slot_priors) {
+  __shared__ ScanLds lds;
+  const int t = threadIdx.x;
+  const int64_t tile = blockIdx.x;
+  const int64_t lo = tile * kPriorTile;
+  const int64_t hi = lo + kPriorTile < n ? lo + kPriorTile : n;
+  const uint32_t head = keys[lo], tailkey = keys[hi - 1];
+  if (head >= P) {  // sorted: nothing but slots that are not live from here on
+    if (!APPLY && t < 2) edges[(2 * tile + t) * kEdgeWords] = kNoKey;
+    return;
+  }
+  scan_init(lds);
+  for (int it = 0; it < kPriorIters; ++it) {
+    const int64_t i = lo + (int64_t)it * kPriorThreads + t;
+    if (lo + (int64_t)it * kPriorThreads >= hi) break;  // uniform over the workgroup
+    const bool valid = i < hi;
+    const uint32_t key = valid ? keys[i] : kNoKey;
+    const bool has = valid && key < P;
+    const bool first = !(valid && i > lo && keys[i - 1] == key);  // of its key in this tile
+    const bool last = valid && (i + 1 == hi || keys[i + 1] != key);
+    const bool edge_run = key == head || key == tailkey;
+    PriorState s = prior_none();
+    if (has) {
+      if (!first) {
+        s = slot_write(vals[i - 1], events, n);
+      } else if (APPLY) {
+        s = key == head      ? state_load(carry + (2 * tile) * kEdgeWords + 1)
+            : key == tailkey ? state_load(carry + (2 * tile + 1) * kEdgeWords + 1)
+                             : prior_from_chain(chain + (int64_t)key * kBaseFloats);
+      }
+    }
+    scan_step(lds, it, key, s);  // the state before element i
+    const uint32_t v = has ? vals[i] : 0u;
+    if (APPLY) {
+      const uint32_t slot = v & kPriorSlotMask;
+      if (has && (int64_t)slot < n) {
+        uint32_t w[4];
+        prior_pick(s, (int)((v >> kPriorModeShift) & 7u), w);
+        v4u x;
+#pragma unroll
+        for (int f = 0; f < 4; ++f) x[f] = w[f];
+        slot_priors[slot] = x;  // one 16-B store; prior_fields_kernel lays them out by field
+      }
+      if (has && last && !edge_run) chain_store(chain, key, prior_combine(s, slot_write(v, events, n)));
+    } else if (valid && (i + 1 == hi || (last && key == head))) {
+      // the last element of the first key, and the tile's last element
+      const PriorState total = has ? prior_combine(s, slot_write(v, events, n)) : prior_none();
+      if (key == head) {
+        edge_store(edges, 2 * tile, key, total);
+        if (i + 1 == hi) edge_store(edges, 2 * tile + 1, key, prior_none());
+      } else {
+        edge_store(edges, 2 * tile + 1, has ? key : kNoKey, total);
+      }
+    }
+  }
+}
+
+// slot-major prior words [M][2K][4] to the field-major priors [M][4][2K]: one lane per match,
+// 16-B loads and stores
+template <int K>
+__global__ void __launch_bounds__(kPriorThreads) prior_fields_kernel(const v4u* __restrict__ slot_priors, int64_t M,
+                                                                     v4u* __restrict__ priors) {
+  constexpr int S = 2 * K;
+  const int64_t m = (int64_t)blockIdx.x * kPriorThreads + threadIdx.x;
+  if (m >= M) return;
+  uint32_t w[4 * S];
+#pragma unroll
+  for (int j = 0; j < S; ++j) {
+    const v4u x = slot_priors[m * S + j];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) w[f * S + j] = x[f];
+  }
+#pragma unroll
+  for (int c = 0; c < S; ++c) {
+    v4u x;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) x[d] = w[4 * c + d];
+    priors[m * S + c] = x;
+  }
+}
+
+// one workgroup over the edges [E] in tile order
+__global__ void __launch_bounds__(kPriorThreads) prior_stitch_kernel(const uint32_t* __restrict__ edges, int64_t E,
+                                                                     uint32_t P, uint32_t* __restrict__ chain,
+                                                                     uint32_t* __restrict__ carry) {
+  __shared__ ScanLds lds;
+  const int t = threadIdx.x;
+  scan_init(lds);
+  const int iters = (int)((E + kPriorThreads - 1) / kPriorThreads);
+  for (int it = 0; it < iters; ++it) {
+    const int64_t e = (int64_t)it * kPriorThreads + t;
+    const uint32_t key = e < E ? edges[e * kEdgeWords] : kNoKey;
+    const bool has = key < P;
+    const bool first = !(e > 0 && e < E && edges[(e - 1) * kEdgeWords] == key);
+    const bool last = !(e + 1 < E && edges[(e + 1) * kEdgeWords] == key);
+    PriorState s = prior_none();
+    if (has)
+      s = first ? prior_from_chain(chain + (int64_t)key * kBaseFloats) : state_load(edges + (e - 1) * kEdgeWords + 1);
+    scan_step(lds, it, key, s);  // the state before edge e's stretch
+    if (has) {
+      state_store(carry + e * kEdgeWords + 1, s);
+      if (last) chain_store(chain, key, prior_combine(s, state_load(edges + e * kEdgeWords + 1)));
+    }
+  }
+}
+
+// What the priors pr [4][2K] of one record resolve to, as preview_kernel (matchmake.hip) sees
+// the same record against a roster: the status, and on kRated p_win0 and p_outcome.
+template <int K>
+__device__ __forceinline__ void predict(const int32_t* r, const float* pr, const v4f* __restrict__ attrs,
+                                        const float* __restrict__ vst, int64_t P, float beta2, float us,
+                                        bool mode_track, uint8_t& gst, float& pw, float& po) {
+  constexpr int S = 2 * K, G = split_group_lanes(K);
+  const uint32_t meta0 = (uint32_t)r[S], meta1 = (uint32_t)r[S + 1];
+  const int n0 = meta_n0(meta0), n1 = meta_n1(meta0);
+  const uint8_t est = early_status<K>(r, P);
+  int32_t id[S];
+  bool inr[S];
+#pragma unroll
+  for (int j = 0; j < S; ++j) {
+    inr[j] = (j < K ? j : j - K) < (j < K ? n0 : n1);
+    id[j] = inr[j] && r[j] >= 0 && (int64_t)r[j] < P ? r[j] : -1;
+  }
+  float ms[S], ss[S], mm[S], sm[S];
+  gst = est;
+  bool failed = false;
+#pragma unroll
+  for (int j = 0; j < S; ++j) {
+    int first = j;  // first slot carrying the same player
+#pragma unroll
+    for (int i = j - 1; i >= 0; --i)
+      if (id[j] >= 0 && id[i] == id[j]) first = i;
+    ms[j] = ss[j] = mm[j] = sm[j] = NAN;
+    if (first != j) {  // a repeated player takes the priors of its first slot
+#pragma unroll
+      for (int i = 0; i < j; ++i) {
+        if (first == i) {
+          ms[j] = ms[i];
+          ss[j] = ss[i];
+          mm[j] = mm[i];
+          sm[j] = sm[i];
+        }
+      }
+    } else if (est == kRated && id[j] >= 0) {
+      float attr[4] = {NAN, NAN, NAN, 0.f};
+      if (pr[j] != pr[j] && attrs != nullptr) {  // seeding only: a NULL shared track
+        const v4f a = attrs[id[j]];
+        attr[0] = a[0];
+        attr[1] = a[1];
+        attr[2] = a[2];
+      }
+      uint32_t flags;
+      float a = NAN, b = NAN, c = NAN, d = NAN;
+      const uint8_t st = player_prior<float>(pr[j], pr[S + j], pr[2 * S + j], pr[3 * S + j], attr, us, vst, a, b, c, d,
+                                             flags);
+      if (st == kRated) {
+        ms[j] = a;
+        ss[j] = b;
+        mm[j] = c;
+        sm[j] = d;
+      } else if (!failed) {  // the first failing slot decides
+        failed = true;
+        gst = st;
+      }
+    }
+  }
+  if (gst == kRated && (n0 == 0 || n1 == 0)) gst = kErrEmptyRoster;
+  // d in slot order, sum sigma^2 as the butterfly: on the mode track for the quality, which
+  // decides kErrNumeric as in preview, and on the chosen track for the prediction
+  float d = 0.f, v[G];
+  bool nonfinite = false;
+#pragma unroll
+  for (int i = 0; i < G; ++i) v[i] = 0.f;
+#pragma unroll
+  for (int i = 0; i < S; ++i) {
+    if (i < K && i < n0) d += mm[i];
+    if (i >= K && i - K < n1) d -= mm[i];
+    if (inr[i] && id[i] >= 0) {
+      v[i] = sm[i] * sm[i];
+      nonfinite = nonfinite || !prior_finite<float>(ms[i], ss[i], mm[i], sm[i]);
+    }
+  }
+  float s2 = butterfly_sum<G>(v);
+  const int n = n0 + n1;
+  const float q = quality_from_sums<float>(n, s2, d, beta2);
+  if (!mode_track) {
+    d = 0.f;
+#pragma unroll
+    for (int i = 0; i < G; ++i) v[i] = 0.f;
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+      if (i < K && i < n0) d += ms[i];
+      if (i >= K && i - K < n1) d -= ms[i];
+      if (inr[i] && id[i] >= 0) v[i] = ss[i] * ss[i];
+    }
+    s2 = butterfly_sum<G>(v);
+  }
+  const float den = (float)n * beta2 + s2;
+  pw = win_probability<float>(d, den);
+  if (gst == kRated && (nonfinite || !isfinite(q) || !isfinite(pw))) gst = kErrNumeric;
+  const bool w0 = meta_winner0(meta1), w1 = meta_winner1(meta1);
+  po = gst == kRated && w0 != w1 ? win_probability<float>(w0 ? d : -d, den) : NAN;
+  if (gst != kRated) pw = NAN;
+}
+
+template <int K>
+__global__ void __launch_bounds__(kScoreThreads) score_kernel(
+    const int32_t* __restrict__ rec, const float* __restrict__ priors, const uint32_t* __restrict__ rows, int64_t W,
+    int64_t M, const v4f* __restrict__ attrs, const float* __restrict__ vst, int64_t P, float beta2, float us,
+    int32_t track, uint32_t modes, unsigned long long* __restrict__ table, int32_t* __restrict__ pred) {
+  constexpr int S = 2 * K;
+  __shared__ unsigned long long part[kScoreTableWords];
+  for (int c = threadIdx.x; c < kScoreTableWords; c += kScoreThreads) part[c] = 0ull;
+  __syncthreads();
+  const int64_t stride = (int64_t)gridDim.x * kScoreThreads;
+  for (int64_t m = (int64_t)blockIdx.x * kScoreThreads + threadIdx.x; m < M; m += stride) {
+    int32_t r[S + 2];
+    load_record<K>(rec, m, r);
+    float pr[4 * S];
+    const v4f* src = reinterpret_cast<const v4f*>(priors + m * (4 * S));
+#pragma unroll
+    for (int c = 0; c < S; ++c) {
+      const v4f x = src[c];
+#pragma unroll
+      for (int d = 0; d < 4; ++d) pr[4 * c + d] = x[d];
+    }
+    const uint32_t st = rows[m * W + 5 * S + 1] & 0xffu;
+    uint8_t gst;
+    float pw, po;
+    predict<K>(r, pr, attrs, vst, P, beta2, us, track == kScoreMode, gst, pw, po);
+    const uint32_t word = score_match(st, (uint32_t)r[S], (uint32_t)r[S + 1], modes, gst, pw, po,
+                                      [&](int c, int64_t x) { atomicAdd(&part[c], (unsigned long long)x); });
+    if (pred != nullptr) {
+      v4u o;
+      o[0] = word;
+      o[1] = __float_as_uint(pw);
+      o[2] = __float_as_uint(po);
+      o[3] = 0u;
+      reinterpret_cast<v4u*>(pred)[m] = o;
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < kScoreTableWords; c += kScoreThreads)
+    if (part[c] != 0ull) atomicAdd(&table[c], part[c]);
+}
+
+__global__ void __launch_bounds__(kScoreThreads) nlog2_kernel(const uint32_t* __restrict__ bits, int64_t n,
+                                                               int64_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * kScoreThreads + threadIdx.x;
+  if (i < n) out[i] = nlog2_q20(bits[i]);
+}
+
+}  // namespace
+
+int launch_nlog2_q20(const uint32_t* bits, int64_t n, int64_t* out, hipStream_t s) {
+  if (n < 0 || n > 0x7fffffffll * kScoreThreads) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(nlog2_kernel, dim3((unsigned)((n + kScoreThreads - 1) / kScoreThreads)), dim3(kScoreThreads), 0, s,
+                     bits, n, out);
+  return (int)hipGetLastError();
+}
+
+static int64_t prior_tiles(int64_t n) { return (n + kPriorTile - 1) / kPriorTile; }
+// edges and carry, 2 * tiles entries each
+size_t prior_edge_bytes(int64_t n) { return (size_t)(2 * 2 * prior_tiles(n) * kEdgeWords) * 4; }
+
+int launch_prior_keys(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t* keys,
+                      uint32_t* vals, uint32_t* events, uint32_t* slot_priors, hipStream_t s) {
+  if (K < 1 || K > kMaxTeamSize || W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll || M * 2 * K > kMaxSlots)
+    return (int)hipErrorInvalidValue;
+  if (M == 0) return 0;
+  const unsigned blocks = (unsigned)((M + kPriorThreads - 1) / kPriorThreads);
+  with_team_size(K, [&](auto k) {
+    hipLaunchKernelGGL(prior_keys_kernel<decltype(k)::value>, dim3(blocks), dim3(kPriorThreads), 0, s, rec,
+                       reinterpret_cast<const uint32_t*>(rows), W, M, P, keys, vals, reinterpret_cast<v4u*>(events),
+                       reinterpret_cast<v4u*>(slot_priors));
+  });
+  return (int)hipGetLastError();
+}
+
+int launch_prior_scan(const uint32_t* keys, const uint32_t* vals, const uint32_t* events, int64_t n, int K, int64_t P,
+                      float* chain, void* edges, uint32_t* slot_priors, float* priors, hipStream_t s) {
+  if (K < 1 || K > kMaxTeamSize || n < 0 || n > kMaxSlots || n % (2 * K) || P < 0 || P > 0x7fffffffll ||
+      reinterpret_cast<uintptr_t>(slot_priors) % 16 != 0 || reinterpret_cast<uintptr_t>(priors) % 16 != 0)
+    return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  v4u* sp = reinterpret_cast<v4u*>(slot_priors);
+  if (P > 0) {
+    const int64_t tiles = prior_tiles(n);
+    uint32_t* e = static_cast<uint32_t*>(edges);
+    uint32_t* carry = e + 2 * tiles * kEdgeWords;
+    uint32_t* ch = reinterpret_cast<uint32_t*>(chain);
+    const v4u* ev = reinterpret_cast<const v4u*>(events);
+    hipLaunchKernelGGL(prior_tile_kernel<false>, dim3((unsigned)tiles), dim3(kPriorThreads), 0, s, keys, vals, ev, n,
+                       (uint32_t)P, ch, e, carry, sp);
+    hipLaunchKernelGGL(prior_stitch_kernel, dim3(1), dim3(kPriorThreads), 0, s, e, 2 * tiles, (uint32_t)P, ch, carry);
+    hipLaunchKernelGGL(prior_tile_kernel<true>, dim3((unsigned)tiles), dim3(kPriorThreads), 0, s, keys, vals, ev, n,
+                       (uint32_t)P, ch, e, carry, sp);
+  }
+  const int64_t M = n / (2 * K);
+  const unsigned blocks = (unsigned)((M + kPriorThreads - 1) / kPriorThreads);
+  with_team_size(K, [&](auto k) {
+    hipLaunchKernelGGL(prior_fields_kernel<decltype(k)::value>, dim3(blocks), dim3(kPriorThreads), 0, s, sp, M,
+                       reinterpret_cast<v4u*>(priors));
+  });
+  return (int)hipGetLastError();
+}
+
+int launch_score(int K, const int32_t* rec, const float* priors, const float* rows, int64_t W, int64_t M,
+                 const float* attrs, const float* vst, int64_t P, float beta2, float unknown_sigma, int track,
+                 uint32_t modes, int64_t* table, int32_t* pred, hipStream_t s) {
+  if (K < 1 || K > kMaxTeamSize || W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll || vst == nullptr ||
+      table == nullptr || (track != kScoreShared && track != kScoreMode) || (modes & ~kScoreAllModes) ||
+      reinterpret_cast<uintptr_t>(attrs) % 16 != 0 || reinterpret_cast<uintptr_t>(priors) % 16 != 0 ||
+      reinterpret_cast<uintptr_t>(pred) % 16 != 0)
+    return (int)hipErrorInvalidValue;
+  if (M == 0) return 0;
+  const int64_t want = (M + kScoreThreads - 1) / kScoreThreads;
+  const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);  // 8 workgroups per CU, then a grid stride
+  with_team_size(K, [&](auto k) {
+    hipLaunchKernelGGL(score_kernel<decltype(k)::value>, dim3(blocks), dim3(kScoreThreads), 0, s, rec, priors,
+                       reinterpret_cast<const uint32_t*>(rows), W, M, reinterpret_cast<const v4f*>(attrs), vst, P,
+                       beta2, unknown_sigma, (int32_t)track, modes, reinterpret_cast<unsigned long long*>(table),
+                       pred);
+  });
+  return (int)hipGetLastError();
+}
+
+}  // namespace ana

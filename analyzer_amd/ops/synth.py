@@ -68,6 +68,29 @@ class StreamSpec:
         return cdf
 
 
+def play_out(rec: torch.Tensor, skill: torch.Tensor, beta: float, seed: int) -> torch.Tensor:
+    """A copy of the records ``rec`` [M, 2K+2] whose winner bits are played out from latent
+    skills ``skill`` [P]: every occupied slot performs skill + N(0, beta^2), a roster's
+    performance is the sum over its slots, and the higher roster wins (never a tie).  The
+    generator's own winners are coin flips, against which every predictor scores exactly one
+    bit per match; these are what a rating can learn.  Plain torch operations, seeded."""
+    S = int(rec.shape[1]) - 2
+    K = S // 2
+    ids = rec[:, :S].to(torch.int64)
+    meta0 = rec[:, S].to(torch.int64)
+    n0, n1 = (meta0 >> 8) & 0xFF, (meta0 >> 16) & 0xFF
+    pos = torch.arange(K, device=rec.device)
+    occupied = torch.cat([pos[None, :] < n0[:, None], pos[None, :] < n1[:, None]], dim=1)
+    occupied &= (ids >= 0) & (ids < skill.shape[0])
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    noise = torch.randn(ids.shape, generator=g, dtype=torch.float64).to(rec.device) * float(beta)
+    perf = (skill.to(torch.float64)[ids.clamp(0, max(0, skill.shape[0] - 1))] + noise) * occupied
+    win0 = perf[:, :K].sum(dim=1) > perf[:, K:].sum(dim=1)
+    out = rec.clone()
+    out[:, S + 1] = (rec[:, S + 1] & ~3) | torch.where(win0, 1, 2).to(rec.dtype)
+    return out
+
+
 def make_roster(spec: RosterSpec, device="cpu"):
     """Return a :class:`Roster` (state [P,32] f32, attrs [P,4] f32) for ``spec``."""
     from .rate import Roster

@@ -24,6 +24,10 @@ for K = 4, 5).  ``records="resident"`` keeps them where the executor writes them
   (``ops/careers.py`` ``CareerTable``, csrc/career.hip, K13): games, wins, first and
   last match, peak and trough, streaks and the quality sum of every player at once,
   without the hits ever leaving the device.  On N ranks it covers the local blocks.
+* ``scorecard(roster0, rec_of)`` scores the ratings as predictions (``ops/scorecard.py``
+  ``Scorecard``, csrc/score.hip, K14): the belief before every match is reconstructed from
+  the rows and the roster the history started from, and the win probability it gives is
+  scored against the outcome.  One rank only.
 * ``export`` / ``load`` move the filled rows through two pinned slots on a copy stream
   into one flat file plus a small JSON header; the round trip is bit-identical.  This
   is how an arena is persisted: checkpoints do not hold arena rows, so a resumed run
@@ -43,6 +47,7 @@ import torch
 from ..ops.careers import CareerTable
 from ..ops.native import native
 from ..ops.rate import RateResult, Roster
+from ..ops.scorecard import Scorecard
 
 # an arena fits when, beside the roster, it leaves at least this fraction of the device's
 # total memory free (the executor's workspaces, the next windows' records and schedules, the
@@ -218,6 +223,21 @@ class RecordArena:
             a = int(self.local_row(lo))
             table.add(rec_of(lo, hi), self.rows[a:a + hi - lo], lo, K=self.K)
         return table
+
+    def scorecard(self, roster0, rec_of: Callable[[int, int], torch.Tensor], **kw) -> Scorecard:
+        """The scorecard (``ops/scorecard.py``, K14) of the filled windows, walked as
+        ``careers`` walks them.  ``roster0``: the roster the arena's history starts from, as
+        it was before ``first_match`` (on a resumed run the checkpoint's roster); ``kw``:
+        ``track``, ``modes``, ``cfg`` of ``Scorecard``.  A chain needs the whole history in
+        order, so on N > 1 ranks this raises."""
+        if self.size > 1:
+            raise ValueError("a scorecard chains the whole history in order: it needs a one-rank arena, this is "
+                             "rank %d of %d" % (self.rank, self.size))
+        card = Scorecard(roster0, **kw)
+        for lo, hi in self.windows():
+            a = int(self.local_row(lo))
+            card.add(rec_of(lo, hi), self.rows[a:a + hi - lo])
+        return card
 
     # ------------------------------------------------------------ sizing
     @staticmethod

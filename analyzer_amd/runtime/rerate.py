@@ -42,6 +42,8 @@ streams a long synthetic history through the engine window by window:
         --window 16000000 --ladder shared,ranked --ladder-top 10 --ladder-rank 17,4242
     python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
         --window 16000000 --matchmake ranked:3:100000
+    python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
+        --window 16000000 --records resident --score mode     # the scorecard of the run (ops/scorecard.py)
 """
 from __future__ import annotations
 
@@ -397,6 +399,14 @@ def rerate_resident(spec: RerateSpec, device=None, checkpoint_dir: Optional[str]
     return metrics, roster, arena
 
 
+def start_roster(spec: RerateSpec, checkpoint_dir: Optional[str], device) -> R.Roster:
+    """The roster a run over ``checkpoint_dir`` starts from, taken before the run: the
+    checkpoint's roster on a resumed run (the arena then starts at its ``first_match``),
+    else the generated one.  This is what ``RecordArena.scorecard`` chains from."""
+    restored = CheckpointManager(checkpoint_dir).latest(device)
+    return restored[0] if restored is not None else make_roster(spec.roster_spec(), device=device)
+
+
 def _timeline(hist: dict, player: int) -> dict:
     """One player's rows of a ``RecordArena.history`` result as JSON-ready lists (NaN -> null)."""
     sel = (hist["player"] == player).nonzero().reshape(-1)
@@ -495,6 +505,11 @@ def main(argv=None) -> int:
                     help="with --careers: score the shared track or each match's mode track")
     ap.add_argument("--careers-modes", default=None, metavar="MODE[,MODE...]",
                     help="with --careers: count only the matches of these modes (default: all)")
+    ap.add_argument("--score", default=None, choices=["mode", "shared"],
+                    help="with --records resident: score the ratings as predictions on each match's mode track or "
+                         "the shared track and print the scorecard after the run (one JSON line; one rank only)")
+    ap.add_argument("--score-modes", default=None, metavar="MODE[,MODE...]",
+                    help="with --score: count only the matches of these modes (default: all)")
     ap.add_argument("--export-records", default=None, metavar="PATH",
                     help="with --records resident: write the arena to PATH (+ PATH.json; .rN appended on N ranks)")
     ap.add_argument("--arena-free-bytes", type=float, default=None,
@@ -530,6 +545,18 @@ def main(argv=None) -> int:
         ap.error("--careers: %s" % e)
     if any(p < 0 or p >= spec.players for p in career_ids):
         ap.error("--careers ids must lie in [0, %d)" % spec.players)
+    if args.score and not resident:
+        ap.error("--score needs --records resident")
+    if args.score_modes and not args.score:
+        ap.error("--score-modes needs --score")
+    if args.score and size > 1:
+        ap.error("--score chains the whole history in order: it runs on one rank")
+    score_modes = [m.strip() for m in (args.score_modes or "").split(",") if m.strip()] or None
+    try:
+        for m in score_modes or ():
+            mode_index(m)
+    except ValueError as e:
+        ap.error("--score-modes: %s" % e)
     if args.ladder_rank and not args.ladder:
         ap.error("--ladder-rank needs --ladder")
     ladder_tracks = [t.strip() for t in (args.ladder or "").split(",") if t.strip()]
@@ -565,6 +592,7 @@ def main(argv=None) -> int:
                       % (plan["arena_bytes_per_rank"], plan["roster_bytes"], plan["left_bytes"], plan["free_bytes"],
                          plan["reserve_bytes"]), file=sys.stderr, flush=True)
                 return 2
+            roster0 = start_roster(spec, args.checkpoint_dir, torch.device(args.device or dev)) if args.score else None
             res, roster, arena = rerate_resident(spec, args.device or dev, args.checkpoint_dir, plan=plan,
                                                  checkpoint_every=args.checkpoint_every,
                                                  fault_kill_after=args.fault_kill_after, comm_dtype=args.comm_dtype,
@@ -601,6 +629,9 @@ def main(argv=None) -> int:
                               modes=career_modes)  # this rank's blocks
         for line in career_lines(table, career_ids):
             print(json.dumps(dict(line, rank=rank)), flush=True)
+    if args.score:
+        card = arena.scorecard(roster0, stream_records(spec, arena.device), track=args.score, modes=score_modes)
+        print(json.dumps({"scorecard": card.summary()}), flush=True)
     if ladder_tracks and rank == 0:  # the roster is replicated after the last merge
         for line in ladder_lines(roster, ladder_tracks, args.ladder_top, ladder_ids):
             print(json.dumps(line), flush=True)
