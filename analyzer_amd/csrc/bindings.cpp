@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "ladder_core.h"
 #include "matchmake_core.h"
+#include "pair_core.h"
 #include "score_core.h"
 #include "select_core.h"
 
@@ -1059,6 +1060,153 @@ Tensor nlog2_q20(Tensor bits) {
   return out;
 }
 
+// K15 (pairs.hip; host mirror host.cpp): the rows of an ordered pair map as (keys [U] int64
+// ascending, counts [U, 4] int32)
+std::tuple<Tensor, Tensor> pair_table_of(const ana::PairMap& map) {
+  const int64_t U = (int64_t)map.size();
+  Tensor keys = torch::empty({U}, torch::kInt64), counts = torch::empty({U, (int64_t)ana::kPairWords}, torch::kInt32);
+  int64_t* k = keys.data_ptr<int64_t>();
+  int32_t* c = counts.data_ptr<int32_t>();
+  for (const auto& row : map) {
+    *k++ = row.first;
+    for (int d = 0; d < ana::kPairWords; ++d) *c++ = row.second[d];
+  }
+  return {keys, counts};
+}
+
+int bit_length(int64_t v) {
+  int bits = 1;
+  while ((v >> bits) != 0) ++bits;
+  return bits;
+}
+
+// the device steps both pair entry points share: n entries with keys ka (a; >= dead: no entry),
+// kb = bkeep (b) and values vals, stably sorted by (a, b) -- on b, then, with a gathered into that
+// order, on a -- and reduced to the table of their distinct (a, b).  The sorts ping-pong between
+// (kb, vals) and two scratch arrays and clobber them, hence bkeep.  src: the counters of an entry
+// are the row src[value] [n, 4], undefined: they are decoded from the value's flags.  One host
+// read, of the number of rows.
+std::tuple<Tensor, Tensor> pair_sort_reduce(Tensor ka, Tensor kb, Tensor bkeep, Tensor vals, int64_t n, int bits,
+                                            uint32_t mask, uint32_t dead, const Tensor& src, hipStream_t s) {
+  const auto i32 = ka.options();
+  Tensor kalt = torch::empty({n}, i32), valt = torch::empty({n}, i32);
+  Tensor ws = torch::empty({(int64_t)ana::radix_sort_workspace_bytes(n)}, i32.dtype(torch::kUInt8));
+  int in_alt = 0;
+  check_hip(ana::launch_radix_sort_pairs(u32p(kb), u32p(vals), u32p(kalt), u32p(valt), n, bits, ws.data_ptr<uint8_t>(),
+                                         &in_alt, s),
+            "pairs: radix sort on b");
+  Tensor k1 = in_alt ? kalt : kb, v1 = in_alt ? valt : vals, k2 = in_alt ? kb : kalt, v2 = in_alt ? vals : valt;
+  // the sorted b keys are no longer needed: a goes where they are
+  check_hip(ana::launch_pair_gather(u32p(ka), u32p(v1), mask, n, u32p(k1), s), "pair_gather (a)");
+  check_hip(ana::launch_radix_sort_pairs(u32p(k1), u32p(v1), u32p(k2), u32p(v2), n, bits, ws.data_ptr<uint8_t>(),
+                                         &in_alt, s),
+            "pairs: radix sort on a");
+  Tensor a = in_alt ? k2 : k1, v = in_alt ? v2 : v1, b = in_alt ? k1 : k2;
+  check_hip(ana::launch_pair_gather(u32p(bkeep), u32p(v), mask, n, u32p(b), s), "pair_gather (b)");
+  const int64_t tiles = ana::pair_tiles(n);
+  Tensor tcounts = torch::empty({tiles}, i32), offsets = torch::empty({tiles + 1}, i32.dtype(torch::kInt64));
+  check_hip(ana::launch_pair_count(u32p(a), u32p(b), n, dead, u32p(tcounts), offsets.data_ptr<int64_t>(), s),
+            "pair_count");
+  const int64_t U = offsets[tiles].item<int64_t>();  // the one synchronisation of a call
+  TORCH_CHECK(U >= 0 && U <= n, "pairs: impossible row count ", U);
+  Tensor keys = torch::empty({U}, i32.dtype(torch::kInt64));
+  Tensor counts = torch::zeros({U, (int64_t)ana::kPairWords}, i32);  // runs cut by an edge are added atomically
+  check_hip(ana::launch_pair_emit(u32p(a), u32p(b), u32p(v), n, dead, src.defined() ? src.data_ptr<int32_t>() : nullptr,
+                                  offsets.data_ptr<int64_t>(), U, keys.data_ptr<int64_t>(), counts.data_ptr<int32_t>(),
+                                  s),
+            "pair_emit");
+  return {keys, counts};
+}
+
+// the pair table (pair_core.h) of one window -- rec [M, 2K+2] joined with its packed output rows
+// [M, W] -- among P players on the modes of the mask, of the players of ``bitmap`` (int32
+// [ceil(P / 32)]; none: of everybody): (keys [U] int64 = a << 32 | b ascending, counts [U, 4] int32
+// = with_games, with_wins, vs_games, vs_wins from a's side).  Dispatches on the tensors' device.
+std::tuple<Tensor, Tensor> pairs_window(Tensor rec, Tensor rows, int64_t P, int64_t modes,
+                                        const c10::optional<Tensor>& bitmap) {
+  const auto dev = rec.device();
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "pairs_window: rec must be [M, 2K+2]");
+  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t M = check_window(rec, rows, K, dev, "pairs_window");
+  TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "pairs_window: P must fit in int32");
+  TORCH_CHECK(modes >= 0 && (modes & ~(int64_t)ana::kPairAllModes) == 0,
+              "pairs_window: the modes mask must name modes 0..5");
+  const int64_t E = ana::pair_entries((int)K);
+  TORCH_CHECK(M <= ana::kMaxSlots / E, "pairs_window: a window holds at most ", ana::kMaxSlots, " entries (", E,
+              " per match)");
+  const uint32_t* bm = nullptr;
+  if (bitmap.has_value() && bitmap->defined()) {
+    check(*bitmap, "bitmap", torch::kInt32, dev);
+    TORCH_CHECK(bitmap->dim() == 1 && bitmap->numel() >= (P + 31) / 32, "pairs_window: bitmap needs ceil(P / 32) words");
+    bm = u32p(*bitmap);
+  }
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
+  if (!dev.is_cuda()) {
+    ana::PairMap map;
+    TORCH_CHECK(ana::host_pairs_add((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                    (uint32_t)modes, bm, map) == 0,
+                "pairs_window: bad arguments");
+    return pair_table_of(map);
+  }
+  const int64_t n = M * E;
+  if (n == 0 || P < 2)  // two different players make an entry
+    return {torch::empty({0}, i32.dtype(torch::kInt64)), torch::empty({0, (int64_t)ana::kPairWords}, i32)};
+  const hipStream_t s = stream_of(rec);
+  Tensor ka = torch::empty({n}, i32), kb = torch::empty({n}, i32), bkeep = torch::empty({n}, i32),
+         vals = torch::empty({n}, i32);
+  // under a filter nearly every entry is dead: only the live ones are written, packed, and sorted
+  Tensor live = bm != nullptr ? torch::zeros({1}, i32) : Tensor();
+  check_hip(ana::launch_pair_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                  (uint32_t)modes, bm, u32p(ka), u32p(kb), u32p(bkeep), u32p(vals),
+                                  live.defined() ? u32p(live) : nullptr, s),
+            "pair_keys");
+  int64_t nl = n;
+  if (live.defined()) {
+    nl = live.item<int32_t>();  // a second synchronisation, which saves the sorts of the dead entries
+    TORCH_CHECK(nl >= 0 && nl <= n, "pairs_window: impossible entry count ", nl);
+    if (nl == 0) return {torch::empty({0}, i32.dtype(torch::kInt64)), torch::empty({0, (int64_t)ana::kPairWords}, i32)};
+  }
+  // bit_length(P): the key P of a dead entry sorts last
+  return pair_sort_reduce(ka.narrow(0, 0, nl), kb.narrow(0, 0, nl), bkeep.narrow(0, 0, nl), vals.narrow(0, 0, nl), nl,
+                          bit_length(P), ana::kPairIndexMask, (uint32_t)P, Tensor(), s);
+}
+
+// the compaction: the tables (keys [n_i] int64, counts [n_i, 4] int32) of one device added into
+// one table.  The rows are concatenated, sorted by key with their indices as values (up to
+// 2^31 - 1 rows) and reduced with the counters gathered at those indices.  P: every id of the
+// keys is below it (it bounds the sort's key bits; 2^31 - 1 is always right).
+std::tuple<Tensor, Tensor> pairs_merge(std::vector<Tensor> keys_list, std::vector<Tensor> counts_list, int64_t P) {
+  TORCH_CHECK(!keys_list.empty() && keys_list.size() == counts_list.size(),
+              "pairs_merge: as many key tensors as count tensors, at least one");
+  TORCH_CHECK(P >= 1 && P <= 0x7fffffffLL, "pairs_merge: P must lie in [1, 2^31)");
+  const auto dev = keys_list[0].device();
+  int64_t n = 0;
+  for (size_t i = 0; i < keys_list.size(); ++i) {
+    check(keys_list[i], "keys", torch::kInt64, dev);
+    check(counts_list[i], "counts", torch::kInt32, dev);
+    TORCH_CHECK(keys_list[i].dim() == 1 && counts_list[i].dim() == 2 &&
+                    counts_list[i].size(0) == keys_list[i].size(0) && counts_list[i].size(1) == ana::kPairWords,
+                "pairs_merge: keys must be [n] and counts [n, 4]");
+    n += keys_list[i].size(0);
+  }
+  TORCH_CHECK(n <= 0x7fffffffLL, "pairs_merge: at most 2^31 - 1 rows");
+  Tensor keys = torch::cat(keys_list), counts = torch::cat(counts_list);
+  if (!dev.is_cuda()) {
+    ana::PairMap map;
+    ana::host_pairs_merge(keys.data_ptr<int64_t>(), counts.data_ptr<int32_t>(), n, map);
+    return pair_table_of(map);
+  }
+  if (n == 0) return {keys, counts};
+  const hipStream_t s = stream_of(keys);
+  const auto i32 = counts.options();
+  Tensor ka = torch::empty({n}, i32), kb = torch::empty({n}, i32), bkeep = torch::empty({n}, i32),
+         vals = torch::empty({n}, i32);
+  check_hip(ana::launch_pair_split(keys.data_ptr<int64_t>(), n, u32p(ka), u32p(kb), u32p(bkeep), u32p(vals), s),
+            "pair_split");
+  // every a is below 2^31: nothing is dead
+  return pair_sort_reduce(ka, kb, bkeep, vals, n, bit_length(P), 0xffffffffu, 0x80000000u, counts, s);
+}
+
 // K11 (ladder.hip; host mirror host.cpp host_ladder): the ladders of the tracks of ``mask``
 // (bit t = granule t) of a roster's state [P, 32], as [order, score, rank] per track in
 // ascending track order: order int32 [R] (best first), score fp32 [R], rank int32 [P]
@@ -1332,6 +1480,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("table"), py::arg("rec"), py::arg("priors"), py::arg("rows"), py::arg("attrs"), py::arg("vst"),
         py::arg("P"), py::arg("beta2"), py::arg("unknown_sigma"), py::arg("track"), py::arg("modes"), py::arg("keep"));
   m.def("nlog2_q20", &nlog2_q20, "K14: -log2(p) * 2^20 of fp32 bit patterns [n] int32 -> [n] int64, integer operations only");
+  m.def("pairs_window", &pairs_window, "K15: the pair table (keys [U] int64 = a << 32 | b ascending, counts [U, 4] int32 = "
+        "with_games, with_wins, vs_games, vs_wins) of one window (rec [M, 2K+2] joined with its packed rows [M, W])",
+        py::arg("rec"), py::arg("rows"), py::arg("P"), py::arg("modes"), py::arg("bitmap") = py::none());
+  m.def("pairs_merge", &pairs_merge, "K15: several pair tables added into one (keys, counts); P: a bound above every id",
+        py::arg("keys_list"), py::arg("counts_list"), py::arg("P") = (int64_t)0x7fffffffLL);
+  m.attr("PAIR_TILE") = ana::kPairTile;
+  m.attr("PAIR_WORDS") = ana::kPairWords;
+  m.def("PAIR_ENTRIES", [](int64_t K) {
+    TORCH_CHECK(K >= 1 && K <= ana::kMaxTeamSize, "PAIR_ENTRIES: K must be 1..5");
+    return (int64_t)ana::pair_entries((int)K);
+  }, "K15: entries of a match of team size K, 2K(2K - 1)");
   m.attr("SCORE_BINS") = ana::kScoreBins;
   m.attr("PRIOR_TILE") = ana::kPriorTile;
   m.attr("NLOG2_CAP") = (int64_t)ana::kNlog2Cap;

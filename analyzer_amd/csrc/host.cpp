@@ -16,6 +16,7 @@
 #include "gen_core.h"
 #include "ladder_core.h"
 #include "matchmake_core.h"
+#include "pair_core.h"
 #include "rate_core.h"
 #include "score_core.h"
 #include "select_core.h"
@@ -389,6 +390,52 @@ int host_careers_add(int K, const int32_t* rec, const float* rows, int64_t W, in
   return with_team_size(K, [&](auto k) {
     careers_add_k<decltype(k)::value>(rec, rows, W, M, base, P, track, score, modes, table);
   }) ? 0 : -1;
+}
+
+// K15: every entry of every match, in (match, entry) order, added to its row of the ordered map
+template <int K>
+static void pairs_add_k(const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
+                        const uint32_t* bitmap, PairMap& table) {
+  constexpr int S = 2 * K, E = pair_entries(K);
+  for (int64_t m = 0; m < M; ++m) {
+    const int32_t* r = rec + m * (S + 2);
+    const uint32_t m0 = (uint32_t)r[S], m1 = (uint32_t)r[S + 1];
+    if (!pair_mode_selected(m0, modes)) continue;
+    bool rated = false, read = false;  // the row is only read for an entry that is live otherwise
+    for (int q = 0; q < E; ++q) {
+      int ja, jb;
+      pair_slots<K>(q, ja, jb);
+      const int32_t a = r[ja], b = r[jb];
+      if (!pair_slot_live<K>(m0, ja, a, P) || !pair_slot_live<K>(m0, jb, b, P) || a == b) continue;
+      if (!pair_filtered(bitmap, a)) continue;
+      if (!read) {
+        uint32_t st;
+        memcpy(&st, rows + m * W + 5 * S + 1, sizeof(st));
+        rated = (st & 0xffu) == kRated;
+        read = true;
+      }
+      if (!rated) break;
+      int32_t c[kPairWords];
+      pair_counters(pair_flags<K>(m1, ja, jb), c);
+      auto& row = table[pair_key((uint32_t)a, (uint32_t)b)];  // a new row is zeroed
+      for (int d = 0; d < kPairWords; ++d) row[d] += c[d];
+    }
+  }
+}
+
+int host_pairs_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
+                   const uint32_t* bitmap, PairMap& table) {
+  if (W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll || (modes & ~kPairAllModes)) return -1;
+  return with_team_size(K, [&](auto k) {
+    pairs_add_k<decltype(k)::value>(rec, rows, W, M, P, modes, bitmap, table);
+  }) ? 0 : -1;
+}
+
+void host_pairs_merge(const int64_t* keys, const int32_t* counts, int64_t n, PairMap& table) {
+  for (int64_t i = 0; i < n; ++i) {
+    auto& row = table[keys[i]];
+    for (int d = 0; d < kPairWords; ++d) row[d] += counts[i * kPairWords + d];
+  }
 }
 
 // K11: the device's three stages on one track -- keys in id order, a stable sort of the

@@ -3,6 +3,9 @@
 
 #include <stdint.h>
 
+#include <array>
+#include <map>
+
 #include "common.h"
 #include "gen_core.h"
 #include "telemetry_core.h"
@@ -75,6 +78,14 @@ int host_priors_add(int K, const int32_t* rec, const float* rows, int64_t W, int
 int host_score_add(int K, const int32_t* rec, const float* priors, const float* rows, int64_t W, int64_t M,
                    const float* attrs, const float* vst, int64_t P, float beta2, float unknown_sigma, int track,
                    uint32_t modes, int64_t* table, int32_t* pred);
+// K15 host mirror (pair_core.h): a plain loop over matches and slot pairs into an ordered map
+// from a << 32 | b to the four counters.  pairs_add adds the entries of rec [M][2K+2] joined with
+// rows [M][W] (bitmap nullable), pairs_merge the rows of a table (keys [n], counts [n][4]); the
+// map's rows in order are the device's (keys, counts), bit for bit.  -1: bad arguments.
+using PairMap = std::map<int64_t, std::array<int32_t, 4>>;
+int host_pairs_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
+                   const uint32_t* bitmap, PairMap& table);
+void host_pairs_merge(const int64_t* keys, const int32_t* counts, int64_t n, PairMap& table);
 // K12 host mirror (matchmake_core.h); out / records as launch_preview / launch_balance /
 // launch_queue_keys (kernels.h) lay them out; attrs may be null.  preview runs rate's own
 // fp64 path (status and quality are the bits host_rate writes); balance chooses the split in

@@ -125,6 +125,40 @@ int launch_score(int K, const int32_t* rec, const float* priors, const float* ro
 // out[i] = nlog2_q20(bits[i]) (score_core.h), i < n
 int launch_nlog2_q20(const uint32_t* bits, int64_t n, int64_t* out, hipStream_t s);
 
+// K15 pairs (pairs.hip, pair_core.h): the pair table of one window rec [M][2K+2] joined with its
+// packed rows [M][W], or of several tables compacted into one.  n entries everywhere; every
+// array is n words unless said otherwise.  Everything is stream-ordered and only reads rec, rows
+// and the source tables; bad sizes or pointers return hipErrorInvalidValue without a launch.
+//   pair_keys   n = M * pair_entries(K) <= kMaxSlots, K in 1..5, P fits int32; bitmap (nullable)
+//               uint32 [ceil(P / 32)]: per entry i = m * E_K + q the key ka[i] (a, or P for a dead
+//               entry), kb[i] = bkeep[i] = b and vals[i] = i | flags.  live_count (nullable; one
+//               zeroed word): only the live entries are written instead, packed from 0 in any
+//               order as vals[pos] = pos | flags, and counted there
+//   pair_split  the same four arrays from int64 keys [n] (a << 32 | b), vals[i] = i
+//   the pairs (kb, vals) are sorted with launch_radix_sort_pairs, pair_gather fetches
+//   out[i] = src[vals[i] & mask] (ka into the sorted order, later b from bkeep), a second sort on
+//   a leaves the entries ordered by (a, b)
+//   pair_count  counts [pair_tiles(n)] = the run heads per tile of the sorted (a, b) (dead: keys
+//               >= dead end the live entries) and offsets [tiles + 1] (8-B aligned) = their
+//               exclusive scan, the number of rows U last: one host read
+//   pair_emit   keys [U] int64 and counts [U][kPairWords] int32 (16-B aligned, zeroed by the
+//               caller); src == nullptr: the counters of an entry are decoded from its value's
+//               flags (n <= kMaxSlots), else they are the 16-B row src[value] (src [n][4])
+constexpr int kPairTile = 2048;  // sorted entries per workgroup of count and emit
+int64_t pair_tiles(int64_t n);
+int launch_pair_keys(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
+                     const uint32_t* bitmap, uint32_t* ka, uint32_t* kb, uint32_t* bkeep, uint32_t* vals,
+                     uint32_t* live_count, hipStream_t s);
+int launch_pair_split(const int64_t* keys, int64_t n, uint32_t* ka, uint32_t* kb, uint32_t* bkeep, uint32_t* vals,
+                      hipStream_t s);
+int launch_pair_gather(const uint32_t* src, const uint32_t* vals, uint32_t mask, int64_t n, uint32_t* out,
+                       hipStream_t s);
+int launch_pair_count(const uint32_t* a, const uint32_t* b, int64_t n, uint32_t dead, uint32_t* counts,
+                      int64_t* offsets, hipStream_t s);
+int launch_pair_emit(const uint32_t* a, const uint32_t* b, const uint32_t* vals, int64_t n, uint32_t dead,
+                     const int32_t* src, const int64_t* offsets, int64_t U, int64_t* keys, int32_t* counts,
+                     hipStream_t s);
+
 // Stable LSD radix sort of (key, value) pairs on the low ``bits`` key bits
 // (radix_sort.hip).  Ping-pongs between the two buffer pairs; *result_in_alt
 // says which holds the result.  ws: radix_sort_workspace_bytes(n) bytes.

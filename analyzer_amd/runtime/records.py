@@ -24,6 +24,9 @@ for K = 4, 5).  ``records="resident"`` keeps them where the executor writes them
   (``ops/careers.py`` ``CareerTable``, csrc/career.hip, K13): games, wins, first and
   last match, peak and trough, streaks and the quality sum of every player at once,
   without the hits ever leaving the device.  On N ranks it covers the local blocks.
+* ``pairs(num_players, rec_of)`` counts, for every two players who shared a rated match, how
+  often they played with and against each other and how it went (``ops/pairs.py``
+  ``PairTable``, csrc/pairs.hip, K15); with ``players=`` only those players' rows are kept.
 * ``scorecard(roster0, rec_of)`` scores the ratings as predictions (``ops/scorecard.py``
   ``Scorecard``, csrc/score.hip, K14): the belief before every match is reconstructed from
   the rows and the roster the history started from, and the win probability it gives is
@@ -46,6 +49,7 @@ import torch
 
 from ..ops.careers import CareerTable
 from ..ops.native import native
+from ..ops.pairs import PairTable
 from ..ops.rate import RateResult, Roster
 from ..ops.scorecard import Scorecard
 
@@ -222,6 +226,16 @@ class RecordArena:
         for lo, hi in self.windows():
             a = int(self.local_row(lo))
             table.add(rec_of(lo, hi), self.rows[a:a + hi - lo], lo, K=self.K)
+        return table
+
+    def pairs(self, num_players: int, rec_of: Callable[[int, int], torch.Tensor], **kw) -> PairTable:
+        """The pair table (``ops/pairs.py``, K15) of the filled windows, walked as ``careers``
+        walks them; ``kw``: ``modes``, ``players``, ``max_entries`` of ``PairTable``.  On N
+        ranks it covers this rank's blocks only."""
+        table = PairTable(num_players, self.device, **kw)
+        for lo, hi in self.windows():
+            a = int(self.local_row(lo))
+            table.add(rec_of(lo, hi), self.rows[a:a + hi - lo], K=self.K)
         return table
 
     def scorecard(self, roster0, rec_of: Callable[[int, int], torch.Tensor], **kw) -> Scorecard:

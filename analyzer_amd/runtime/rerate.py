@@ -44,6 +44,8 @@ streams a long synthetic history through the engine window by window:
         --window 16000000 --matchmake ranked:3:100000
     python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
         --window 16000000 --records resident --score mode     # the scorecard of the run (ops/scorecard.py)
+    python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
+        --window 16000000 --records resident --pairs 17,4242  # whom they play with and against (ops/pairs.py)
 """
 from __future__ import annotations
 
@@ -428,6 +430,21 @@ def career_lines(table, ids) -> list:
                  **{name: _num(vals[i]) for name, vals in cols.items()}) for i, p in enumerate(ids)]
 
 
+def pair_lines(table, ids, top: int = 5) -> list:
+    """One JSON-ready dict per player of ``ids`` from a ``PairTable`` (ops/pairs.py): the number
+    of distinct players it shared a rated match with, and its ``top`` most frequent team mates
+    and opponents with its own wins next to them."""
+    lines = []
+    for p in ids:
+        line = {"pairs": int(p), "partners": table.n_partners(p)}
+        for name, relation in (("with", "with"), ("against", "against")):
+            cols = {k: v.cpu().tolist() for k, v in table.partners(p, relation, top=top).items()}
+            line[name] = [{"player": q, "games": g, "wins": w}
+                          for q, g, w in zip(cols["player"], cols["games"], cols["wins"])]
+        lines.append(line)
+    return lines
+
+
 def _num(v: float):
     return None if v != v else v  # NaN -> null
 
@@ -505,6 +522,13 @@ def main(argv=None) -> int:
                     help="with --careers: score the shared track or each match's mode track")
     ap.add_argument("--careers-modes", default=None, metavar="MODE[,MODE...]",
                     help="with --careers: count only the matches of these modes (default: all)")
+    ap.add_argument("--pairs", default=None, metavar="ID[,ID...]",
+                    help="with --records resident: print whom each player played with and against after the run "
+                         "(JSON lines): the distinct partners and the most frequent team mates and opponents")
+    ap.add_argument("--pairs-modes", default=None, metavar="MODE[,MODE...]",
+                    help="with --pairs: count only the matches of these modes (default: all)")
+    ap.add_argument("--pairs-top", type=int, default=None, metavar="N",
+                    help="with --pairs: the N most frequent team mates and opponents (default 5)")
     ap.add_argument("--score", default=None, choices=["mode", "shared"],
                     help="with --records resident: score the ratings as predictions on each match's mode track or "
                          "the shared track and print the scorecard after the run (one JSON line; one rank only)")
@@ -545,6 +569,22 @@ def main(argv=None) -> int:
         ap.error("--careers: %s" % e)
     if any(p < 0 or p >= spec.players for p in career_ids):
         ap.error("--careers ids must lie in [0, %d)" % spec.players)
+    if args.pairs and not resident:
+        ap.error("--pairs needs --records resident")
+    if (args.pairs_modes or args.pairs_top is not None) and not args.pairs:
+        ap.error("--pairs-modes and --pairs-top need --pairs")
+    pair_modes = [m.strip() for m in (args.pairs_modes or "").split(",") if m.strip()] or None
+    pair_top = 5 if args.pairs_top is None else args.pairs_top
+    try:
+        pair_ids = [int(p) for p in (args.pairs or "").split(",") if p.strip()]
+        for m in pair_modes or ():
+            mode_index(m)
+    except ValueError as e:
+        ap.error("--pairs: %s" % e)
+    if any(p < 0 or p >= spec.players for p in pair_ids):
+        ap.error("--pairs ids must lie in [0, %d)" % spec.players)
+    if pair_top < 0:
+        ap.error("--pairs-top must be >= 0")
     if args.score and not resident:
         ap.error("--score needs --records resident")
     if args.score_modes and not args.score:
@@ -628,6 +668,12 @@ def main(argv=None) -> int:
         table = arena.careers(spec.players, stream_records(spec, arena.device), track=args.careers_track,
                               modes=career_modes)  # this rank's blocks
         for line in career_lines(table, career_ids):
+            print(json.dumps(dict(line, rank=rank)), flush=True)
+    if pair_ids:
+        # the player filter: however long the history, only these players' rows are held
+        table = arena.pairs(spec.players, stream_records(spec, arena.device), modes=pair_modes,
+                            players=pair_ids)  # this rank's blocks
+        for line in pair_lines(table, pair_ids, pair_top):
             print(json.dumps(dict(line, rank=rank)), flush=True)
     if args.score:
         card = arena.scorecard(roster0, stream_records(spec, arena.device), track=args.score, modes=score_modes)
