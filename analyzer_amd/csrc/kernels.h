@@ -170,7 +170,10 @@ int launch_radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, 
 // of the stream's slots by player fused with the record decode and the links.
 // ws: radix_sort_workspace_bytes(M * 2K) bytes; ka..vb: M * 2K words each.
 // deps [M] (zeroed by the first kernel), ctrl[0..nz) (zeroed), epoch_bump (+1): the
-// schedule's fill work, folded into that kernel (null / 0: skipped)
+// schedule's fill work, folded into that kernel (null / 0: skipped).  sort_nt (ANA_SORT_NT wins):
+// non-temporal accesses of the sort, 0 none, 1 all, 2 loads only -- what a caller asks for whose
+// prepass runs beside the executor, so with >= 1 the chain path also writes its links as whole
+// lines (sched_unpartition), which costs the executor less and the prepass itself more
 int launch_sched_sort(int K, const int32_t* rec, int64_t M, uint32_t num_players, uint32_t* ka,
                       uint32_t* va, uint32_t* kb, uint32_t* vb, void* ws, uint32_t* link,
                       hipStream_t s, int32_t* deps = nullptr, uint32_t* ctrl = nullptr, int nz = 0,

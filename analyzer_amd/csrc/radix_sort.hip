@@ -30,6 +30,19 @@
 // (4 launches and ~1.84 GB per 10M 3v3 window instead of 9 and ~3.0 GB; 1.22-1.25 ms alone
 // against 1.60-1.64, the config 2 step 0.10-0.12 ms shorter, profiles/r7/sched_chain_ab.log).
 // Larger rosters keep the three LSD passes; ANA_SCHED_CHAIN=0 selects them for A/B.
+//
+// Beside the executor the links of that path leave as whole lines (round 8; a prepass with nothing
+// beside it keeps the direct stores, see sched_sort_k).  sched_chain writes link[slot] there:
+// 60M random 4-B stores per window, one fabric write request each, beside an executor whose time
+// is the latency of its own requests.  The new variant writes each link at the slot's position in its
+// bucket, in place over the bucket's keys and one tile late through an LDS buffer, so that a link
+// resolved by the next tile still leaves inside a coalesced run; 6.2 % of the links (deferred
+// past the next tile, or to the final flush) remain single stores.  sched_unpartition, one
+// workgroup per input tile, then reads the tile's 256 runs back through the partition's own
+// offset table and writes link[] in slot order with 16-B stores.  5 launches and ~2.56 GB per
+// window, but 10.3M write requests from the two kernels instead of 58.8M: alone the prepass is
+// slower (1.54-1.57 against 1.22-1.26 ms), beside the executor the config 2 step is 0.27-0.37 ms
+// shorter (profiles/r8/links_whole_lines_ab.log).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -548,14 +561,16 @@ sched_runs_fixup(const RunEnds* __restrict__ bnd, int64_t tiles, int nd, const i
 // and after the last tile T is flushed with kNoMatch links.  Every link is written once,
 // with plain stores (L2 write combining, see radix_downsweep); no workgroup waits on
 // another.  KS > 0: no partition in front (top = 0, <= 4096 players): the one workgroup
-// decodes its keys from the records and does the SchedInit duties.
+// decodes its keys from the records, does the SchedInit duties and writes link[slot] itself
+// (its windows are small).  LINES: the links of a bucket in bucket order instead, see below.
 constexpr int kChainLowBits = 12;
 constexpr int kChainRB = 6;
 constexpr uint32_t kChainEmpty = 0xffffffffu;
 constexpr bool kChainDefault = true;  // ANA_SCHED_CHAIN overrides (launch_sched_sort)
 
 // one stable ranking round of the tile held in registers ((wave, item, lane) order = tile
-// order) by kChainRB key bits at `shift`, scattered into skey / sval
+// order) by kChainRB key bits at `shift`, scattered into skey / sval (VALS = false: keys only)
+template <bool VALS = true>
 __device__ __forceinline__ void chain_sort_round(const uint32_t (&key)[kItems], const uint32_t (&val)[kItems],
                                                  int shift, uint32_t* skey, uint32_t* sval,
                                                  uint32_t (*wcnt)[1 << kChainRB], uint32_t* tstart,
@@ -603,24 +618,40 @@ __device__ __forceinline__ void chain_sort_round(const uint32_t (&key)[kItems], 
     const uint32_t d = (key[it] >> shift) & (kR - 1);
     const uint32_t pos = tstart[d] + wcnt[wv][d] + rank[it];
     skey[pos] = key[it];
-    sval[pos] = val[it];
+    if constexpr (VALS) sval[pos] = val[it];
   }
   __syncthreads();
 }
 
-// (84 KB of LDS: one workgroup per CU, two waves per SIMD.  The link loops are unrolled by 2
-// only: fully unrolled the compiler takes 236 VGPRs, and two such waves no longer fit on a
-// SIMD beside a wave of the executor; 164 do)
-template <int KS, int NT>
+// LINES (a bucket of the partition, KS == 0): the links leave as whole lines.  A slot's link is written
+// at the slot's POSITION in the partitioned arrays, in place over the bucket's keys (a tile's
+// keys are dead once it is in registers, and only this workgroup reads its bucket), and
+// sched_unpartition below carries it to link[slot].  The sort key of an element is its low key
+// bits | its position in the tile << low (inside a bucket only the low bits differ), so a sorted
+// element knows where it sat.  The links of a tile go through lbuf, indexed by that position,
+// and leave one tile late: while tile i is linked, a deferred link of tile i - 1 is resolved in
+// lbuf, one of an older tile with a plain store at its bucket position (T holds bucket positions);
+// then lbuf is written out in position order, minus the positions still deferred (kLinkDeferred:
+// masked, not written, so every link word has exactly one writer), and takes the links of tile i.
+// Slots without state that share a chained bucket with players (256 buckets) get kLinkSkip.
+constexpr uint32_t kLinkDeferred = 0xfffffffeu;  // lbuf only
+constexpr uint32_t kLinkSkip = 0xffffffffu;      // no link for this slot: sched_unpartition leaves link[slot] alone
+
+// (LINES: 116 KB of LDS, else 84 KB: one workgroup per CU, two waves per SIMD.  The link
+// loops are unrolled by 2 only: fully unrolled the compiler takes 236 VGPRs, and two such waves
+// no longer fit on a SIMD beside a wave of the executor)
+template <int KS, int NT, bool LINES>
 __global__ void __launch_bounds__(kThreads)
-sched_chain(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
+sched_chain(uint32_t* kio, const uint32_t* __restrict__ vin,
             const int32_t* __restrict__ rec, uint32_t kend, int64_t n, int low,
             const uint32_t* __restrict__ totals, int slots_per_match, uint32_t* __restrict__ link,
             uint32_t vlo, uint32_t vhi, int64_t matches, SchedInit init) {
   constexpr int kR = 1 << kChainRB;
+  static_assert(!LINES || KS == 0, "bucket positions need the partition");
   __shared__ uint32_t skey[kTile];
   __shared__ uint32_t sval[kTile];
-  __shared__ uint32_t last_seen[1 << kChainLowBits];  // T: slot | kLinkHasPred, kChainEmpty
+  __shared__ uint32_t lbuf[LINES ? kTile : 1];        // links of the previous tile, by position
+  __shared__ uint32_t last_seen[1 << kChainLowBits];  // T: slot (LINES: bucket position) | kLinkHasPred, kChainEmpty
   __shared__ uint32_t wcnt[kWaves][kR];
   __shared__ uint32_t tstart[kR];
   __shared__ uint32_t wsum[kWaves];
@@ -641,6 +672,7 @@ sched_chain(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
     start = below;
     cnt = totals[blockIdx.x];
   }
+  const uint32_t kbase = LINES ? (uint32_t)blockIdx.x << low : 0u;  // the bucket's key bits above `low`
   for (int64_t base = 0; base < cnt; base += kTile) {
     const int64_t nvalid = cnt - base < kTile ? cnt - base : kTile;
     uint32_t key[kItems], val[kItems];
@@ -659,64 +691,211 @@ sched_chain(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
       if constexpr (KS > 0) {
         key[it] = valid ? sval[p] : 0xffffffffu;
         val[it] = (uint32_t)idx;
-      } else {
-        key[it] = valid ? ld32<NT>(kin + idx) : 0xffffffffu;
+      } else if constexpr (!LINES) {
+        key[it] = valid ? ld32<NT>(kio + idx) : 0xffffffffu;
         val[it] = valid ? ld32<NT>(vin + idx) : 0u;
+      } else {
+        // the slots stay in tile order (sval[p]); only the keys are sorted, and each carries its p
+        key[it] = valid ? (ld32<NT>(kio + idx) & lmask) | (uint32_t)p << low : 0xffffffffu;
+        if (valid) sval[p] = ld32<NT>(vin + idx);
       }
     }
-    chain_sort_round(key, val, 0, skey, sval, wcnt, tstart, wsum);
+    chain_sort_round<!LINES>(key, val, 0, skey, sval, wcnt, tstart, wsum);
     if (low > kChainRB) {  // (uniform)
 #pragma unroll
       for (int it = 0; it < kItems; ++it) {
         const int p = (wv * kItems + it) * 64 + lane;
         key[it] = skey[p];
-        val[it] = sval[p];
+        if constexpr (!LINES) val[it] = sval[p];
       }
-      chain_sort_round(key, val, kChainRB, skey, sval, wcnt, tstart, wsum);
+      chain_sort_round<!LINES>(key, val, kChainRB, skey, sval, wcnt, tstart, wsum);
     }
     // the tile is sorted by player, each player's slots in time order
     uint32_t is_last = 0u, has = 0u;  // bit k: element k of this thread ends a run / has a predecessor
+    if constexpr (!LINES) {
 #pragma unroll 2
-    for (int k = 0; k < kItems; ++k) {
-      const int i = k * kThreads + tid;
-      if (i < nvalid) {
-        const uint32_t kk = skey[i];
-        if (kk < kend) {
-          const uint32_t v = sval[i];
-          const bool next = i + 1 < nvalid && skey[i + 1] == kk;
-          bool pred = i > 0 && skey[i - 1] == kk;
-          if (!pred) {  // first of its run: the player's last slot of an earlier tile links here
-            const uint32_t t = last_seen[kk & lmask];
-            if (t != kChainEmpty) {
-              pred = true;
-              const uint32_t ts = t & kMatchMask;
-              if (ts >= vlo && ts < vhi) link[ts] = v / (uint32_t)slots_per_match | (t & kLinkHasPred);
+      for (int k = 0; k < kItems; ++k) {
+        const int i = k * kThreads + tid;
+        if (i < nvalid) {
+          const uint32_t kk = skey[i];
+          if (kk < kend) {
+            const uint32_t v = sval[i];
+            const bool next = i + 1 < nvalid && skey[i + 1] == kk;
+            bool pred = i > 0 && skey[i - 1] == kk;
+            if (!pred) {  // first of its run: the player's last slot of an earlier tile links here
+              const uint32_t t = last_seen[kk & lmask];
+              if (t != kChainEmpty) {
+                pred = true;
+                const uint32_t ts = t & kMatchMask;
+                if (ts >= vlo && ts < vhi) link[ts] = v / (uint32_t)slots_per_match | (t & kLinkHasPred);
+              }
             }
+            if (next) {
+              if (v >= vlo && v < vhi)  // this part's slot range (link_parts)
+                link[v] = sval[i + 1] / (uint32_t)slots_per_match | (pred ? kLinkHasPred : 0u);
+            } else {
+              is_last |= 1u << k;
+            }
+            if (pred) has |= 1u << k;
           }
-          if (next) {
-            if (v >= vlo && v < vhi)  // this part's slot range (link_parts)
-              link[v] = sval[i + 1] / (uint32_t)slots_per_match | (pred ? kLinkHasPred : 0u);
-          } else {
-            is_last |= 1u << k;
-          }
-          if (pred) has |= 1u << k;
         }
       }
-    }
-    __syncthreads();  // every first has read T before the lasts replace its entries
+      __syncthreads();  // every first has read T before the lasts replace its entries
 #pragma unroll 2
-    for (int k = 0; k < kItems; ++k) {
-      const int i = k * kThreads + tid;
-      if (is_last >> k & 1u) last_seen[skey[i] & lmask] = sval[i] | (has >> k & 1u ? kLinkHasPred : 0u);
+      for (int k = 0; k < kItems; ++k) {
+        const int i = k * kThreads + tid;
+        if (is_last >> k & 1u) last_seen[skey[i] & lmask] = sval[i] | (has >> k & 1u ? kLinkHasPred : 0u);
+      }
+    } else {
+      const int64_t prev = base - kTile;  // bucket position of lbuf[0]: the previous tile
+#pragma unroll 2
+      for (int k = 0; k < kItems; ++k) {
+        const int i = k * kThreads + tid;
+        if (i < nvalid) {
+          const uint32_t kl = skey[i] & lmask;
+          if ((kbase | kl) < kend) {
+            const bool next = i + 1 < nvalid && (skey[i + 1] & lmask) == kl;
+            bool pred = i > 0 && (skey[i - 1] & lmask) == kl;
+            if (!pred) {  // first of its run: the link T deferred for this player
+              const uint32_t t = last_seen[kl];
+              if (t != kChainEmpty) {
+                pred = true;
+                const int64_t tp = t & kMatchMask;
+                const uint32_t w = sval[skey[i] >> low] / (uint32_t)slots_per_match | (t & kLinkHasPred);
+                if (tp >= prev) lbuf[tp - prev] = w;  // still in LDS: leaves with its tile's lines
+                else kio[start + tp] = w;            // an older tile: the one random store left
+              }
+            }
+            if (!next) is_last |= 1u << k;
+            if (pred) has |= 1u << k;
+          }
+        }
+      }
+      __syncthreads();  // lbuf holds every link of the previous tile that this tile resolves
+      if (base > 0) {   // (a previous tile is a full tile)
+#pragma unroll 2
+        for (int k = 0; k < kItems; ++k) {
+          const int j = k * kThreads + tid;
+          const uint32_t w = lbuf[j];
+          if (w != kLinkDeferred) st32<NT>(kio + start + prev + j, w);
+        }
+      }
+#pragma unroll 2
+      for (int k = 0; k < kItems; ++k) {
+        const int i = k * kThreads + tid;
+        if (is_last >> k & 1u) {
+          const uint32_t kk = skey[i];
+          last_seen[kk & lmask] = (uint32_t)(base + (kk >> low)) | (has >> k & 1u ? kLinkHasPred : 0u);
+        }
+      }
+      __syncthreads();  // lbuf is written out
+#pragma unroll 2
+      for (int k = 0; k < kItems; ++k) {
+        const int i = k * kThreads + tid;
+        if (i < nvalid) {
+          const uint32_t kk = skey[i];
+          uint32_t w = kLinkSkip;
+          if ((kbase | (kk & lmask)) < kend)
+            w = is_last >> k & 1u ? kLinkDeferred
+                                  : sval[skey[i + 1] >> low] / (uint32_t)slots_per_match |
+                                        (has >> k & 1u ? kLinkHasPred : 0u);
+          lbuf[kk >> low] = w;
+        }
+      }
     }
     __syncthreads();  // skey / sval are rewritten by the next tile
   }
   __syncthreads();
-  for (int e = tid; e <= (int)lmask; e += kThreads) {  // the last slot of every player seen
-    const uint32_t t = last_seen[e];
-    if (t != kChainEmpty) {
-      const uint32_t ts = t & kMatchMask;
-      if (ts >= vlo && ts < vhi) link[ts] = kNoMatch | (t & kLinkHasPred);
+  if constexpr (!LINES) {
+    for (int e = tid; e <= (int)lmask; e += kThreads) {  // the last slot of every player seen
+      const uint32_t t = last_seen[e];
+      if (t != kChainEmpty) {
+        const uint32_t ts = t & kMatchMask;
+        if (ts >= vlo && ts < vhi) link[ts] = kNoMatch | (t & kLinkHasPred);
+      }
+    }
+  } else {
+    // the last slot of every player seen; those of the last tile leave with its lines
+    const int64_t lastb = cnt > 0 ? (cnt - 1) / kTile * kTile : 0;
+    for (int e = tid; e <= (int)lmask; e += kThreads) {
+      const uint32_t t = last_seen[e];
+      if (t != kChainEmpty) {
+        const int64_t tp = t & kMatchMask;
+        const uint32_t w = kNoMatch | (t & kLinkHasPred);
+        if (tp >= lastb) lbuf[tp - lastb] = w;
+        else kio[start + tp] = w;
+      }
+    }
+    __syncthreads();
+    for (int64_t j = tid; j < cnt - lastb; j += kThreads) st32<NT>(kio + start + lastb + j, lbuf[j]);
+  }
+}
+
+// Links from bucket order to slot order (after sched_chain<0>): one workgroup per INPUT tile of
+// the partition.  The partition is stable, so the pairs a tile sent to one bucket are one run
+// of that bucket, in slot order, at the offset radix_downsweep stored them to: this kernel is
+// its store loop turned into loads.  It reads the tile's runs of slots (vo) and of links (lk:
+// what sched_chain left in place of the keys), places each link in LDS at slot - tile start
+// and writes link[tile] as whole lines.  Slots that get no link -- the buckets nobody chains
+// (d >= nb) and kLinkSkip -- are left alone.
+template <int RB, int NT>
+__global__ void __launch_bounds__(kThreads)
+sched_unpartition(const uint32_t* __restrict__ lk, const uint32_t* __restrict__ vo, int64_t n,
+                  const uint32_t* __restrict__ counts, const uint32_t* __restrict__ totals,
+                  int64_t tiles, int nb, uint32_t* __restrict__ link) {
+  constexpr int kR = 1 << RB;
+  static_assert(kR <= kThreads, "one digit per thread");
+  __shared__ uint32_t out[kTile];
+  __shared__ uint32_t tstart[kR];  // start of each digit's run in the (sorted) tile
+  __shared__ uint32_t gstart[kR];  // ... and in the partitioned arrays
+  __shared__ uint32_t wsum[kWaves];
+  const int tid = threadIdx.x;
+  const int64_t tile = xcd_tile(tiles);
+  const int64_t base = tile * kTile;
+  const int64_t nvalid = n - base < kTile ? n - base : kTile;
+  uint32_t c0 = 0u, len = 0u;
+  if (tid < nb) {
+    c0 = counts[(int64_t)tid * tiles + tile];
+    len = (tile + 1 < tiles ? counts[(int64_t)tid * tiles + tile + 1] : totals[tid]) - c0;
+  }
+  uint32_t nchain = 0u;
+  const uint32_t g = block_exclusive_scan(tid < kR ? totals[tid] : 0u, wsum, nullptr);
+  const uint32_t ts = block_exclusive_scan(len, wsum, &nchain);
+  if (tid < kR) {
+    gstart[tid] = g + c0;
+    tstart[tid] = ts;  // (digits >= nb: nchain, past every element)
+  }
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) out[k * kThreads + tid] = kLinkSkip;
+  __syncthreads();
+#pragma unroll 4
+  for (int k = 0; k < kItems; ++k) {
+    const uint32_t i = k * kThreads + tid;
+    if (i < nchain) {
+      uint32_t d = 0u;  // the last digit whose run starts at or before i (the runs before it may be empty)
+#pragma unroll
+      for (uint32_t step = kR >> 1; step > 0u; step >>= 1)
+        if (tstart[d + step] <= i) d += step;
+      const int64_t o = (int64_t)gstart[d] + (i - tstart[d]);
+      if (o < n) {
+        const uint32_t at = ld32<NT>(vo + o) - (uint32_t)base;
+        if (at < (uint32_t)kTile) out[at] = ld32<NT>(lk + o);
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kItems / 4; ++k) {
+    const int j = (k * kThreads + tid) * 4;
+    const uint4 w = *reinterpret_cast<const uint4*>(out + j);
+    const bool all = w.x != kLinkSkip && w.y != kLinkSkip && w.z != kLinkSkip && w.w != kLinkSkip;
+    if (j + 4 <= nvalid && all && (reinterpret_cast<uintptr_t>(link + base + j) & 15u) == 0u) {
+      *reinterpret_cast<uint4*>(link + base + j) = w;
+    } else {
+      if (j < nvalid && w.x != kLinkSkip) link[base + j] = w.x;
+      if (j + 1 < nvalid && w.y != kLinkSkip) link[base + j + 1] = w.y;
+      if (j + 2 < nvalid && w.z != kLinkSkip) link[base + j + 2] = w.z;
+      if (j + 3 < nvalid && w.w != kLinkSkip) link[base + j + 3] = w.w;
     }
   }
 }
@@ -767,7 +946,6 @@ static void sched_sort_k(const int32_t* rec, int64_t n, uint32_t kend, int bits,
   uint32_t *ko = kb, *vo = vb;
   if (chain) {  // one partition by the bits above `low`, then one workgroup per bucket (sched_chain)
     const int low = bits < kChainLowBits ? bits : kChainLowBits, top = bits - low;
-    const int parts = link_parts(n);
     if (top > 0) {
       // Players fill the buckets below nb.  The slots without state (key kend: 2 % of the
       // matches of the bench stream, five buckets' worth) would all land in kend's bucket and
@@ -780,13 +958,29 @@ static void sched_sort_k(const int32_t* rec, int64_t n, uint32_t kend, int bits,
       hipLaunchKernelGGL(radix_rowscan, dim3(kR), block, 0, s, counts, tiles, totals);
       hipLaunchKernelGGL((radix_downsweep<K, false, RB, NT>), grid, block, 0, s, nullptr, nullptr, rec, kend, ko,
                          vo, n, low, counts, totals, tiles, S, nullptr, 0u, 0xffffffffu, 1, nullptr, 0, knone);
-      for (int q = 0; q < parts; ++q)
-        hipLaunchKernelGGL((sched_chain<0, NT>), dim3(nb), block, 0, s, ko, vo, nullptr, kend, n, low,
-                           totals, S, link, (uint32_t)(n * q / parts), (uint32_t)(n * (q + 1) / parts),
-                           n / S, SchedInit{});
+      // A prepass beside the executor (its caller streams the sort's input with non-temporal
+      // loads: sort_nt / ANA_SORT_NT >= 1) writes the links as whole lines: the executor pays
+      // for the prepass's write requests, and the step is 0.27-0.37 ms shorter.  A prepass with
+      // nothing beside it keeps the direct stores: alone they are 0.32 ms faster per window
+      // (config 2 with ANA_PREPASS_SERIAL=1: 6.32-6.37 against 6.69-6.72 ms with whole lines).
+      if constexpr (NT != 0 && kR <= kThreads) {  // (the 10-bit experiment never takes the chain path)
+        // once, whatever ANA_LINK_PARTS says: there is no randomly written link array to keep
+        // inside the Infinity Cache
+        hipLaunchKernelGGL((sched_chain<0, NT, true>), dim3(nb), block, 0, s, ko, vo, nullptr, kend, n, low,
+                           totals, S, nullptr, 0u, 0xffffffffu, n / S, SchedInit{});
+        hipLaunchKernelGGL((sched_unpartition<RB, NT>), grid, block, 0, s, ko, vo, n, counts, totals, tiles,
+                           (int)nb, link);
+      } else {
+        const int parts = link_parts(n);
+        for (int q = 0; q < parts; ++q)
+          hipLaunchKernelGGL((sched_chain<0, NT, false>), dim3(nb), block, 0, s, ko, vo, nullptr, kend, n, low,
+                             totals, S, link, (uint32_t)(n * q / parts), (uint32_t)(n * (q + 1) / parts),
+                             n / S, SchedInit{});
+      }
     } else {
+      const int parts = link_parts(n);
       for (int q = 0; q < parts; ++q)
-        hipLaunchKernelGGL((sched_chain<K, NT>), dim3(1), block, 0, s, nullptr, nullptr, rec, kend, n, low,
+        hipLaunchKernelGGL((sched_chain<K, NT, false>), dim3(1), block, 0, s, nullptr, nullptr, rec, kend, n, low,
                            nullptr, S, link, (uint32_t)(n * q / parts), (uint32_t)(n * (q + 1) / parts),
                            n / S, q == 0 ? init : SchedInit{});
     }
