@@ -78,6 +78,32 @@ int64_t check_rec(const Tensor& rec, int64_t K, const torch::Device& dev, const 
   return rec.size(0);
 }
 
+// one window as K10, K13, K14 and K15 take it: rec [M, 2K+2] and its packed output rows [M, W]
+// on dev, aligned for the device's vector loads -> M
+int64_t check_window(const Tensor& rec, const Tensor& rows, int64_t K, const torch::Device& dev, const char* what) {
+  const int64_t M = check_rec(rec, K, dev, what);
+  check(rows, "rows", torch::kFloat32, dev);
+  TORCH_CHECK(rows.dim() == 2 && rows.size(0) == M && rows.size(1) >= 10 * K + 2 && rows.size(1) % 4 == 0, what,
+              ": rows must be the packed [M, W] output rows of rec's matches");
+  if (dev.is_cuda())
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(rec.data_ptr()) % (K % 2 == 0 ? 8 : 16) == 0 &&
+                    reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0,
+                what, ": rec and rows must be 16-B aligned");
+  return M;
+}
+
+// the slots of a window are sort values (K13, K14)
+void check_slots(int64_t M, int64_t K, const char* what) {
+  TORCH_CHECK(M * 2 * K <= ana::kMaxSlots, what, ": a window holds at most ", ana::kMaxSlots, " slots");
+}
+
+// the key bits of a sort by player: P itself, the key of a slot without one, sorts last
+int bit_length(int64_t v) {
+  int bits = 1;
+  while ((v >> bits) != 0) ++bits;
+  return bits;
+}
+
 // roster state [P, 32] fp32 -> P
 int64_t check_state(const Tensor& state, const torch::Device& dev, const char* what) {
   check(state, "state", torch::kFloat32, dev);
@@ -862,20 +888,13 @@ int64_t records_digest_scratch(int64_t K) { return (int64_t)ana::records_digest_
 // Dispatches on the tensors' device; the device path synchronises once to size hits exactly.
 Tensor records_select(Tensor rec, Tensor rows, int64_t base, int64_t P, Tensor bitmap) {
   const auto dev = rec.device();
-  check(rec, "rec", torch::kInt32, dev);
-  check(rows, "rows", torch::kFloat32, dev);
+  TORCH_CHECK(rec.dim() == 2, "records_select: rec must be [M, 2K+2] with K in 1..5");
+  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t M = check_window(rec, rows, K, dev, "records_select");  // K outside 1..5 and odd widths included
   check(bitmap, "bitmap", torch::kInt32, dev);
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) <= 12 && rec.size(1) % 2 == 0,
-              "records_select: rec must be [M, 2K+2] with K in 1..5");
-  const int64_t M = rec.size(0), K = (rec.size(1) - 2) / 2;
-  TORCH_CHECK(rows.dim() == 2 && rows.size(0) == M && rows.size(1) >= 10 * K + 2 && rows.size(1) % 4 == 0,
-              "records_select: rows must be the packed [M, W] output rows of rec's matches");
   TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "records_select: P must fit in int32");
   TORCH_CHECK(base >= 0, "records_select: base must be >= 0");
   TORCH_CHECK(bitmap.dim() == 1 && bitmap.numel() >= (P + 31) / 32, "records_select: bitmap needs ceil(P / 32) words");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(rec.data_ptr()) % (K % 2 == 0 ? 8 : 16) == 0 &&
-                  reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0,
-              "records_select: rec and rows must be 16-B aligned");
   const uint32_t* bm = u32p(bitmap);
   const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
   if (!dev.is_cuda()) {
@@ -902,6 +921,17 @@ Tensor records_select(Tensor rec, Tensor rows, int64_t base, int64_t P, Tensor b
   return hits;
 }
 
+// the scan between the count and emit launches of K10 and K15 on its own, for the tests
+Tensor tile_offsets(Tensor counts) {
+  TORCH_CHECK(counts.is_cuda(), "tile_offsets: counts must be on the device");
+  check(counts, "counts", torch::kInt32, counts.device());
+  TORCH_CHECK(counts.dim() == 1, "tile_offsets: counts must be [T]");
+  Tensor offsets = torch::empty({counts.numel() + 1}, counts.options().dtype(torch::kInt64));
+  check_hip(ana::launch_tile_offsets(u32p(counts), counts.numel(), offsets.data_ptr<int64_t>(), stream_of(counts)),
+            "tile_offsets");
+  return offsets;
+}
+
 // K13 (career.hip; host mirror host.cpp host_careers_add): folds the games of one window -- rec
 // [M, 2K+2] joined with its packed output rows [M, W], base the global index of match 0 -- into
 // the career table [P, 16] int32 in place (career_core.h).  Dispatches on the tensors' device;
@@ -911,18 +941,15 @@ void careers_add(Tensor table, Tensor rec, Tensor rows, int64_t base, int64_t P,
   const auto dev = table.device();
   TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "careers_add: rec must be [M, 2K+2]");
   const int64_t K = (rec.size(1) - 2) / 2;
-  const int64_t M = check_rec(rec, K, dev, "careers_add");
-  check(rows, "rows", torch::kFloat32, dev);
+  const int64_t M = check_window(rec, rows, K, dev, "careers_add");
+  check_slots(M, K, "careers_add");
   TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "careers_add: P must fit in int32");
   check_rows(table, "table", P, ana::kCareerWords, dev, torch::kInt32);
-  TORCH_CHECK(rows.dim() == 2 && rows.size(0) == M && rows.size(1) >= 10 * K + 2 && rows.size(1) % 4 == 0,
-              "careers_add: rows must be the packed [M, W] output rows of rec's matches");
   TORCH_CHECK(base >= 0, "careers_add: base must be >= 0");
   TORCH_CHECK(track == ana::kCareerShared || track == ana::kCareerMode, "careers_add: unknown track ", track);
   TORCH_CHECK(score == ana::kLadderConservative || score == ana::kLadderMu, "careers_add: unknown score ", score);
   TORCH_CHECK(modes >= 0 && (modes & ~(int64_t)ana::kCareerAllModes) == 0,
               "careers_add: the modes mask must name modes 0..5");
-  TORCH_CHECK(M * 2 * K <= ana::kMaxSlots, "careers_add: a window holds at most ", ana::kMaxSlots, " slots");
   if (M == 0 || P == 0) return;
   if (!dev.is_cuda()) {
     TORCH_CHECK(ana::host_careers_add((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, base,
@@ -930,10 +957,7 @@ void careers_add(Tensor table, Tensor rec, Tensor rows, int64_t base, int64_t P,
                 "careers_add: bad arguments");
     return;
   }
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(rec.data_ptr()) % (K % 2 == 0 ? 8 : 16) == 0 &&
-                  reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0,
-              "careers_add: rec, rows and table must be 16-B aligned");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0, "careers_add: table must be 16-B aligned");
   const hipStream_t s = stream_of(table);
   const int64_t n = M * 2 * K;
   const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
@@ -942,28 +966,11 @@ void careers_add(Tensor table, Tensor rec, Tensor rows, int64_t base, int64_t P,
   check_hip(ana::launch_career_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
                                     (int)track, (int)score, (uint32_t)modes, u32p(keys), u32p(vals), u32p(events), s),
             "career_keys");
-  int bits = 1;
-  while ((P >> bits) != 0) ++bits;  // bit_length(P): the key P of a slot that is no game sorts last
-  const auto sorted = sort_pairs_on_stream(keys, vals, n, bits, s);
+  const auto sorted = sort_pairs_on_stream(keys, vals, n, bit_length(P), s);
   Tensor edges = torch::empty({(int64_t)ana::career_edge_bytes(n)}, i32.dtype(torch::kUInt8));
   check_hip(ana::launch_career_fold(u32p(sorted[0]), u32p(sorted[1]), u32p(events), n, (int)K, base, P,
                                     table.data_ptr<int32_t>(), edges.data_ptr<uint8_t>(), s),
             "career_fold");
-}
-
-// K14 (score.hip; host mirrors host.cpp): the operands both calls share -- rec [M, 2K+2] and its
-// packed rows [M, W] on dev, aligned for the device's vector loads -> M
-int64_t check_window(const Tensor& rec, const Tensor& rows, int64_t K, const torch::Device& dev, const char* what) {
-  const int64_t M = check_rec(rec, K, dev, what);
-  check(rows, "rows", torch::kFloat32, dev);
-  TORCH_CHECK(rows.dim() == 2 && rows.size(0) == M && rows.size(1) >= 10 * K + 2 && rows.size(1) % 4 == 0, what,
-              ": rows must be the packed [M, W] output rows of rec's matches");
-  TORCH_CHECK(M * 2 * K <= ana::kMaxSlots, what, ": a window holds at most ", ana::kMaxSlots, " slots");
-  if (dev.is_cuda())
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(rec.data_ptr()) % (K % 2 == 0 ? 8 : 16) == 0 &&
-                    reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0,
-                what, ": rec and rows must be 16-B aligned");
-  return M;
 }
 
 // priors [M, 4 * 2K] fp32 (field-major: shared mu, sigma, mode mu, sigma) of one window against
@@ -975,6 +982,7 @@ Tensor priors_add(Tensor chain, Tensor rec, Tensor rows) {
   TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "priors_add: rec must be [M, 2K+2]");
   const int64_t K = (rec.size(1) - 2) / 2;
   const int64_t M = check_window(rec, rows, K, dev, "priors_add");
+  check_slots(M, K, "priors_add");
   TORCH_CHECK(chain.dim() == 2, "priors_add: chain must be [P, 16]");
   const int64_t P = chain.size(0);
   TORCH_CHECK(P <= 0x7fffffffLL, "priors_add: P must fit in int32");
@@ -996,9 +1004,7 @@ Tensor priors_add(Tensor chain, Tensor rec, Tensor rows) {
   check_hip(ana::launch_prior_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
                                    u32p(keys), u32p(vals), u32p(events), u32p(slot_priors), s),
             "prior_keys");
-  int bits = 1;
-  while ((P >> bits) != 0) ++bits;  // bit_length(P): the key P of a slot that is not live sorts last
-  const auto sorted = P > 0 ? sort_pairs_on_stream(keys, vals, n, bits, s) : std::vector<Tensor>{keys, vals};
+  const auto sorted = P > 0 ? sort_pairs_on_stream(keys, vals, n, bit_length(P), s) : std::vector<Tensor>{keys, vals};
   Tensor edges = torch::empty({(int64_t)ana::prior_edge_bytes(n)}, i32.dtype(torch::kUInt8));
   check_hip(ana::launch_prior_scan(u32p(sorted[0]), u32p(sorted[1]), u32p(events), n, (int)K, P,
                                    chain.data_ptr<float>(), edges.data_ptr<uint8_t>(), u32p(slot_priors),
@@ -1016,6 +1022,7 @@ Tensor score_add(Tensor table, Tensor rec, Tensor priors, Tensor rows, c10::opti
   TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "score_add: rec must be [M, 2K+2]");
   const int64_t K = (rec.size(1) - 2) / 2;
   const int64_t M = check_window(rec, rows, K, dev, "score_add");
+  check_slots(M, K, "score_add");
   check(table, "table", torch::kInt64, dev);
   TORCH_CHECK(table.numel() == ana::kScoreTableWords, "score_add: table must be [6, 33, 4]");
   check_rows(priors, "priors", M, 8 * K, dev);
@@ -1072,12 +1079,6 @@ std::tuple<Tensor, Tensor> pair_table_of(const ana::PairMap& map) {
     for (int d = 0; d < ana::kPairWords; ++d) *c++ = row.second[d];
   }
   return {keys, counts};
-}
-
-int bit_length(int64_t v) {
-  int bits = 1;
-  while ((v >> bits) != 0) ++bits;
-  return bits;
 }
 
 // the device steps both pair entry points share: n entries with keys ka (a; >= dead: no entry),
@@ -1454,6 +1455,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("records_select", &records_select, "K10: hits [n, 12] int32 of the bitmap's players in a window's records "
         "joined with its packed output rows, ascending (match, slot)", py::arg("rec"), py::arg("rows"),
         py::arg("base"), py::arg("P"), py::arg("bitmap"));
+  m.def("tile_offsets", &tile_offsets, "offsets [T + 1] int64 = exclusive scan of counts [T] int32 read as unsigned, "
+        "the total last (the scan between K10's and K15's count and emit; device only)", py::arg("counts"));
   m.def("ladder", &ladder, "K11: [order, score, rank] per track of the mask (bit t = granule t) of a roster's state: "
         "descending score, ties by ascending id, rank -1 = unranked", py::arg("state"), py::arg("mask"),
         py::arg("score"), py::arg("max_sigma"));

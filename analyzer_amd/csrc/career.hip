@@ -14,9 +14,9 @@
 //   sort    launch_radix_sort_pairs on bit_length(P) bits: stable, so each player's games
 //           come out in (match, slot) order, and the slots that are no game sort last.
 //   fold    one workgroup per tile of kCareerTile sorted elements, one lane per element per
-//           iteration: the lane gathers its event and a segmented inclusive scan under
-//           career_combine (shuffles inside the wave, LDS across the waves, a carry across
-//           the iterations) leaves a player's whole run in the lane of its last element.
+//           iteration: the lane gathers its event and the segmented inclusive scan of
+//           scan_dev.h under career_combine leaves a player's whole run in the lane of its
+//           last element.
 //           A run strictly inside the tile is folded into its row by that lane.  The runs
 //           of the tile's first and last key go to edges[2 * tile + 0 / 1]: they may go on
 //           in a neighbour tile.  Cost per element is the same for every key distribution.
@@ -31,16 +31,15 @@
 #include "common.h"
 #include "kernels.h"
 #include "record_dev.h"
+#include "scan_dev.h"
 
 namespace ana {
 
 namespace {
 
 constexpr int kCareerThreads = 256;
-constexpr int kCareerWaves = kCareerThreads / 64;
 constexpr int kCareerIters = kCareerTile / kCareerThreads;
 static_assert(kCareerTile % kCareerThreads == 0, "a tile is a whole number of iterations");
-constexpr uint32_t kNoKey = 0xffffffffu;  // above every sort key (keys are <= P < 2^31)
 // an edge: [key, -, CareerRun]
 constexpr int kEdgeWords = 20;
 static_assert(sizeof(CareerRun) == 4 * (kEdgeWords - 2), "an edge holds a key and a run");
@@ -91,99 +90,14 @@ __global__ void __launch_bounds__(kCareerThreads) career_keys_kernel(
   }
 }
 
-__device__ __forceinline__ CareerRun shfl_up_run(const CareerRun& a, int o) {
-  CareerRun c;
-  c.games = __shfl_up(a.games, o, 64);
-  c.wins = __shfl_up(a.wins, o, 64);
-  c.afk = __shfl_up(a.afk, o, 64);
-  c.invalid = __shfl_up(a.invalid, o, 64);
-  c.first = __shfl_up((long long)a.first, o, 64);
-  c.last = __shfl_up((long long)a.last, o, 64);
-  c.peak_match = __shfl_up((long long)a.peak_match, o, 64);
-  c.quality_sum = __shfl_up((long long)a.quality_sum, o, 64);
-  c.peak = __shfl_up(a.peak, o, 64);
-  c.trough = __shfl_up(a.trough, o, 64);
-  c.lead_win = __shfl_up(a.lead_win, o, 64);
-  c.trail_win = __shfl_up(a.trail_win, o, 64);
-  c.trail_loss = __shfl_up(a.trail_loss, o, 64);
-  c.best_win = __shfl_up(a.best_win, o, 64);
-  return c;
-}
-
-// field by field, so a run stays in registers on either side
-__device__ __forceinline__ void run_store(CareerRun* dst, const CareerRun& a) {
-  dst->games = a.games;
-  dst->wins = a.wins;
-  dst->afk = a.afk;
-  dst->invalid = a.invalid;
-  dst->first = a.first;
-  dst->last = a.last;
-  dst->peak_match = a.peak_match;
-  dst->quality_sum = a.quality_sum;
-  dst->peak = a.peak;
-  dst->trough = a.trough;
-  dst->lead_win = a.lead_win;
-  dst->trail_win = a.trail_win;
-  dst->trail_loss = a.trail_loss;
-  dst->best_win = a.best_win;
-}
-__device__ __forceinline__ CareerRun run_load(const CareerRun* src) {
-  CareerRun c;
-  c.games = src->games;
-  c.wins = src->wins;
-  c.afk = src->afk;
-  c.invalid = src->invalid;
-  c.first = src->first;
-  c.last = src->last;
-  c.peak_match = src->peak_match;
-  c.quality_sum = src->quality_sum;
-  c.peak = src->peak;
-  c.trough = src->trough;
-  c.lead_win = src->lead_win;
-  c.trail_win = src->trail_win;
-  c.trail_loss = src->trail_loss;
-  c.best_win = src->best_win;
-  return c;
-}
-
-// LDS of the workgroup scan, double-buffered over the iterations (one barrier each):
-// entry 0 is the carry of the earlier iterations, entry 1 + w the total of wave w
-struct ScanLds {
-  uint32_t key[2][kCareerWaves + 1];
-  CareerRun run[2][kCareerWaves + 1];
+struct CareerOps {
+  static __device__ __forceinline__ CareerRun combine(const CareerRun& a, const CareerRun& b) {
+    return career_combine(a, b);
+  }
+  static __device__ __forceinline__ CareerRun identity() { return career_empty(); }
 };
-
-__device__ __forceinline__ void scan_init(ScanLds& lds) {
-  if (threadIdx.x == 0) lds.key[0][0] = kNoKey;
-}
-
-// Iteration ``it`` of a segmented inclusive scan over elements in ascending key order, one
-// per lane: on return ``run`` covers the lane's key from its first element of this workgroup
-// (or its first element at all) up to the lane.  Lanes past the end pass kNoKey.
-__device__ __forceinline__ void scan_step(ScanLds& lds, int it, uint32_t key, CareerRun& run) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = it & 1;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t ok = __shfl_up(key, o, 64);
-    const CareerRun orun = shfl_up_run(run, o);
-    if (lane >= o && ok == key) run = career_combine(orun, run);
-  }
-  if (lane == 63) {
-    lds.key[b][1 + wave] = key;
-    run_store(&lds.run[b][1 + wave], run);
-  }
-  __syncthreads();
-  // keys ascend, so the entries that match are the last ones before this wave
-  CareerRun before = career_empty();
-#pragma unroll
-  for (int e = 0; e < kCareerWaves; ++e)
-    if (e <= wave && lds.key[b][e] == key) before = career_combine(before, run_load(&lds.run[b][e]));
-  run = career_combine(before, run);
-  if (t == kCareerThreads - 1) {  // read after the next barrier, written after this one
-    lds.key[b ^ 1][0] = key;
-    run_store(&lds.run[b ^ 1][0], run);
-  }
-}
+// on return from step a lane's run covers its key from the key's first element of this workgroup
+typedef SegScan<kCareerThreads, CareerRun, CareerOps> CareerScan;
 
 __device__ __forceinline__ void row_add(int32_t* __restrict__ table, uint32_t p, const CareerRun& run) {
   v4i* q = reinterpret_cast<v4i*>(table + (int64_t)p * kCareerWords);
@@ -207,13 +121,13 @@ __device__ __forceinline__ void row_add(int32_t* __restrict__ table, uint32_t p,
 __device__ __forceinline__ void edge_store(int32_t* __restrict__ edges, int64_t e, uint32_t key, const CareerRun& run) {
   int32_t* w = edges + e * kEdgeWords;
   w[0] = (int32_t)key;
-  run_store(reinterpret_cast<CareerRun*>(w + 2), run);
+  state_store(reinterpret_cast<CareerRun*>(w + 2), run);
 }
 
 __global__ void __launch_bounds__(kCareerThreads) career_fold_kernel(
     const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, const v2u* __restrict__ events, int64_t n,
     uint32_t S, int64_t base, uint32_t P, int32_t* __restrict__ table, int32_t* __restrict__ edges) {
-  __shared__ ScanLds lds;
+  __shared__ CareerScan::Lds lds;
   const int t = threadIdx.x;
   const int64_t lo = (int64_t)blockIdx.x * kCareerTile;
   const int64_t hi = lo + kCareerTile < n ? lo + kCareerTile : n;
@@ -222,7 +136,7 @@ __global__ void __launch_bounds__(kCareerThreads) career_fold_kernel(
     if (t < 2) edges[(2 * (int64_t)blockIdx.x + t) * kEdgeWords] = (int32_t)kNoKey;
     return;
   }
-  scan_init(lds);
+  CareerScan::init(lds);
   for (int it = 0; it < kCareerIters; ++it) {
     const int64_t i = lo + (int64_t)it * kCareerThreads + t;
     if (lo + (int64_t)it * kCareerThreads >= hi) break;  // uniform over the workgroup
@@ -237,7 +151,7 @@ __global__ void __launch_bounds__(kCareerThreads) career_fold_kernel(
         run = career_game(ev[0], ev[1], base + (int64_t)(v / S));
       }
     }
-    scan_step(lds, it, key, run);
+    CareerScan::step(lds, it, key, run);
     const bool tail = i + 1 == hi;
     if (valid && (tail || next != key)) {  // the last element of its key in this tile
       if (key == head) {
@@ -255,9 +169,9 @@ __global__ void __launch_bounds__(kCareerThreads) career_fold_kernel(
 // one workgroup over the edges [E] in tile order
 __global__ void __launch_bounds__(kCareerThreads) career_stitch_kernel(const int32_t* __restrict__ edges, int64_t E,
                                                                        uint32_t P, int32_t* __restrict__ table) {
-  __shared__ ScanLds lds;
+  __shared__ CareerScan::Lds lds;
   const int t = threadIdx.x;
-  scan_init(lds);
+  CareerScan::init(lds);
   const int iters = (int)((E + kCareerThreads - 1) / kCareerThreads);
   // the edge of the next iteration is loaded ahead of this one's scan: the loop is one
   // workgroup's latency chain
@@ -268,14 +182,14 @@ __global__ void __launch_bounds__(kCareerThreads) career_stitch_kernel(const int
     key_n = e < E ? (uint32_t)edges[e * kEdgeWords] : kNoKey;
     next_n = e + 1 < E ? (uint32_t)edges[(e + 1) * kEdgeWords] : kNoKey;
     run_n = career_empty();
-    if (key_n < P) run_n = run_load(reinterpret_cast<const CareerRun*>(edges + e * kEdgeWords + 2));
+    if (key_n < P) run_n = state_load(reinterpret_cast<const CareerRun*>(edges + e * kEdgeWords + 2));
   };
   load(0);
   for (int it = 0; it < iters; ++it) {
     const uint32_t key = key_n, next = next_n;
     CareerRun run = run_n;
     if (it + 1 < iters) load(it + 1);
-    scan_step(lds, it, key, run);
+    CareerScan::step(lds, it, key, run);
     if (key < P && next != key) row_add(table, key, run);
   }
 }

@@ -36,6 +36,11 @@ size_t records_digest_scratch_doubles(int K);
 int launch_records_digest(int K, const float* rows, int64_t M, int64_t W, double* scratch, double* out,
                           int64_t* hist, hipStream_t s);
 
+// Tile offsets (scan.hip): offsets [tiles + 1] (8-B aligned) = the exclusive scan of counts
+// [tiles] read as unsigned, in 64 bits, the total last; one workgroup.  tiles == 0 writes
+// offsets[0] = 0.  K10 and K15 run it between their count and emit launches.
+int launch_tile_offsets(const uint32_t* counts, int64_t tiles, int64_t* offsets, hipStream_t s);
+
 // K10 records_select (select.hip, select_core.h): the hits [n][kHitWords] int32 of the players
 // of ``bitmap`` (uint32 [ceil(P / 32)]) in a window's records rec [M][2K+2] joined with its
 // packed output rows [M][W], in ascending (match, slot) order; base: global index of match 0.

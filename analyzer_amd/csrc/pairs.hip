@@ -22,7 +22,7 @@
 //           result is ordered by (a, b).  A second gather lays b out in the sorted order.
 //   count   one workgroup per tile of kPairTile sorted entries: the run heads of the tile.
 //           A head is a live entry whose a OR b differs from its predecessor's.
-//   scan    one workgroup: exclusive scan of the tile counts, the total U last; the host
+//   scan    launch_tile_offsets: exclusive scan of the tile counts, the total U last; the host
 //           reads U once to size the table.
 //   emit    the same tile walk.  A head writes its row's key.  The counters of an entry are
 //           decoded from its value's flags (a window) or loaded as the 16-B row at its
@@ -39,6 +39,7 @@
 #include "kernels.h"
 #include "pair_core.h"
 #include "record_dev.h"
+#include "scan_dev.h"
 #include "select_core.h"
 
 namespace ana {
@@ -46,7 +47,6 @@ namespace ana {
 namespace {
 
 constexpr int kPairThreads = 256;
-constexpr int kPairWaves = kPairThreads / 64;
 constexpr int kPairIters = kPairTile / kPairThreads;
 static_assert(kPairTile % kPairThreads == 0, "a tile is a whole number of iterations");
 
@@ -147,49 +147,7 @@ __global__ void __launch_bounds__(kPairThreads) pair_count_kernel(const uint32_t
       if (a_i < dead && pair_head(a, b, i, a_i, b[i])) ++heads;
     }
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) heads += __shfl_xor(heads, o, 64);
-  __shared__ uint32_t wsum[kPairWaves];
-  if ((t & 63) == 0) wsum[t >> 6] = heads;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t s = 0u;
-#pragma unroll
-    for (int w = 0; w < kPairWaves; ++w) s += wsum[w];
-    counts[blockIdx.x] = s;
-  }
-}
-
-// one workgroup: lane l owns the tiles [l * per, (l + 1) * per)
-__global__ void __launch_bounds__(kPairThreads) pair_scan_kernel(const uint32_t* __restrict__ counts, int64_t tiles,
-                                                                 int64_t* __restrict__ offsets) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t per = (tiles + kPairThreads - 1) / kPairThreads;
-  const int64_t lo = (int64_t)t * per < tiles ? (int64_t)t * per : tiles;
-  const int64_t hi = lo + per < tiles ? lo + per : tiles;
-  int64_t own = 0;
-  for (int64_t i = lo; i < hi; ++i) own += counts[i];
-  int64_t incl = own;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t v = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += v;
-  }
-  __shared__ int64_t wsum[kPairWaves];
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int64_t before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kPairWaves; ++w) {
-    before += w < wave ? wsum[w] : 0;
-    total += wsum[w];
-  }
-  int64_t run = before + incl - own;
-  for (int64_t i = lo; i < hi; ++i) {
-    offsets[i] = run;
-    run += counts[i];
-  }
-  if (t == 0) offsets[tiles] = total;
+  block_sum_store<kPairThreads>(heads, counts + blockIdx.x);
 }
 
 // kGather: the counters of an entry are the row src[value] (compaction), else its value's flags
@@ -198,12 +156,10 @@ __global__ void __launch_bounds__(kPairThreads) pair_emit_kernel(
     const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, const uint32_t* __restrict__ vals, int64_t n,
     uint32_t dead, const v4i* __restrict__ src, const int64_t* __restrict__ offsets, int64_t U,
     int64_t* __restrict__ keys, int32_t* __restrict__ counts) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, lane = t & 63;
   const int64_t lo = (int64_t)blockIdx.x * kPairTile;
   if (a[lo] >= dead) return;  // uniform over the workgroup
   int64_t run = offsets[blockIdx.x];  // run heads before this tile
-  // per-wave head counts, double-buffered over the iterations: one barrier per iteration
-  __shared__ int wsum[2][kPairWaves];
   for (int it = 0; it < kPairIters; ++it) {
     const int64_t i0 = lo + (int64_t)it * kPairThreads;
     if (i0 >= n) break;  // uniform over the workgroup
@@ -214,15 +170,8 @@ __global__ void __launch_bounds__(kPairThreads) pair_emit_kernel(
     const bool head = valid && pair_head(a, b, i, a_i, b_i);
     const unsigned long long bal = __ballot(head);
     const int incl = __popcll(bal & (~0ull >> (63 - lane)));  // heads of this wave up to this lane
-    if (lane == 63) wsum[it & 1][wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kPairWaves; ++w) {
-      const int s = wsum[it & 1][w];
-      before += w < wave ? s : 0;
-      total += s;
-    }
+    int total;
+    const int before = block_offset<kPairThreads>(it, incl, total);
     const int64_t row = run + before + incl - 1;  // a run without a head here goes on from an earlier wave or tile
     run += total;
     int32_t c[kPairWords] = {0, 0, 0, 0};
@@ -328,8 +277,7 @@ int launch_pair_count(const uint32_t* a, const uint32_t* b, int64_t n, uint32_t 
   const int64_t tiles = pair_tiles(n);
   if (tiles > 0)
     hipLaunchKernelGGL(pair_count_kernel, dim3((unsigned)tiles), dim3(kPairThreads), 0, s, a, b, n, dead, counts);
-  hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(kPairThreads), 0, s, counts, tiles, offsets);
-  return (int)hipGetLastError();
+  return launch_tile_offsets(counts, tiles, offsets, s);
 }
 
 int launch_pair_emit(const uint32_t* a, const uint32_t* b, const uint32_t* vals, int64_t n, uint32_t dead,

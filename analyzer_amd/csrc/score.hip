@@ -15,8 +15,9 @@
 //   sort       launch_radix_sort_pairs on bit_length(P) bits: stable, so each player's slots
 //              come out in (match, slot) order.
 //   summaries  one workgroup per tile of kPriorTile sorted elements.  The exclusive scan is
-//              run as an inclusive scan of shifted terms: element i contributes the write of
-//              element i - 1 of the same key, so the scanned value is the state before i and
+//              run as the inclusive scan of scan_dev.h over shifted terms: element i
+//              contributes the write of element i - 1 of the same key, so the scanned value
+//              is the state before i and
 //              one 16-B gather per element feeds it.  The runs of the tile's first and last
 //              key, the only ones that can go on in a neighbour tile, leave their totals
 //              (without any starting state) in edges[2 * tile + 0 / 1].
@@ -58,6 +59,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "record_dev.h"
+#include "scan_dev.h"
 #include "score_core.h"
 
 namespace ana {
@@ -65,10 +67,8 @@ namespace ana {
 namespace {
 
 constexpr int kPriorThreads = 256;
-constexpr int kPriorWaves = kPriorThreads / 64;
 constexpr int kPriorIters = kPriorTile / kPriorThreads;
 static_assert(kPriorTile % kPriorThreads == 0, "a tile is a whole number of iterations");
-constexpr uint32_t kNoKey = 0xffffffffu;  // above every sort key (keys are <= P < 2^31)
 // an edge or a carry: [key, mask, w[14]], 64 B
 constexpr int kEdgeWords = 16;
 static_assert(sizeof(PriorState) == 4 * (kEdgeWords - 1), "an edge holds a key and a state");
@@ -131,65 +131,22 @@ __global__ void __launch_bounds__(kPriorThreads) prior_keys_kernel(
   }
 }
 
-__device__ __forceinline__ PriorState shfl_up_state(const PriorState& a, int o) {
-  PriorState c;
-  c.mask = __shfl_up(a.mask, o, 64);
-#pragma unroll
-  for (int i = 0; i < 2 * kTracks; ++i) c.w[i] = __shfl_up(a.w[i], o, 64);
-  return c;
-}
-
-// word by word, so a state stays in registers on either side
-__device__ __forceinline__ void state_store(uint32_t* dst, const PriorState& a) {
-  dst[0] = a.mask;
-#pragma unroll
-  for (int i = 0; i < 2 * kTracks; ++i) dst[1 + i] = a.w[i];
-}
-__device__ __forceinline__ PriorState state_load(const uint32_t* src) {
-  PriorState c;
-  c.mask = src[0];
-#pragma unroll
-  for (int i = 0; i < 2 * kTracks; ++i) c.w[i] = src[1 + i];
-  return c;
-}
-
-// LDS of the workgroup scan, double-buffered over the iterations (one barrier each):
-// entry 0 is the carry of the earlier iterations, entry 1 + w the total of wave w
-struct ScanLds {
-  uint32_t key[2][kPriorWaves + 1];
-  uint32_t st[2][kPriorWaves + 1][kEdgeWords - 1];
+struct PriorOps {
+  static __device__ __forceinline__ PriorState combine(const PriorState& a, const PriorState& b) {
+    return prior_combine(a, b);
+  }
+  static __device__ __forceinline__ PriorState identity() { return prior_none(); }
 };
+// on return from step a lane's state covers the terms of its key from the first one this
+// workgroup saw up to the lane's
+typedef SegScan<kPriorThreads, PriorState, PriorOps> PriorScan;
 
-__device__ __forceinline__ void scan_init(ScanLds& lds) {
-  if (threadIdx.x == 0) lds.key[0][0] = kNoKey;
+// the state of the edge or carry entry e: the words behind its key
+__device__ __forceinline__ const PriorState* edge_state(const uint32_t* entries, int64_t e) {
+  return reinterpret_cast<const PriorState*>(entries + e * kEdgeWords + 1);
 }
-
-// Iteration ``it`` of a segmented inclusive scan over terms in ascending key order, one per
-// lane: on return ``s`` covers the terms of the lane's key from the first one this workgroup
-// saw up to the lane's.  Lanes past the end pass kNoKey.
-__device__ __forceinline__ void scan_step(ScanLds& lds, int it, uint32_t key, PriorState& s) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = it & 1;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t ok = __shfl_up(key, o, 64);
-    const PriorState os = shfl_up_state(s, o);
-    if (lane >= o && ok == key) s = prior_combine(os, s);
-  }
-  if (lane == 63) {
-    lds.key[b][1 + wave] = key;
-    state_store(lds.st[b][1 + wave], s);
-  }
-  __syncthreads();
-  // keys ascend, so the entries that match are the last ones before this wave
-  PriorState before = prior_none();
-#pragma unroll
-  for (int e = 0; e < kPriorWaves; ++e)
-    if (e <= wave && lds.key[b][e] == key) before = prior_combine(before, state_load(lds.st[b][e]));
-  s = prior_combine(before, s);
-  if (t == kPriorThreads - 1) {  // read after the next barrier, written after this one
-    lds.key[b ^ 1][0] = key;
-    state_store(lds.st[b ^ 1][0], s);
-  }
+__device__ __forceinline__ PriorState* edge_state(uint32_t* entries, int64_t e) {
+  return reinterpret_cast<PriorState*>(entries + e * kEdgeWords + 1);
 }
 
 // the write of the slot with sort value v (prior_none() when it does not write)
@@ -208,7 +165,7 @@ __device__ __forceinline__ void chain_store(uint32_t* __restrict__ chain, uint32
 
 __device__ __forceinline__ void edge_store(uint32_t* __restrict__ edges, int64_t e, uint32_t key, const PriorState& s) {
   edges[e * kEdgeWords] = key;
-  state_store(edges + e * kEdgeWords + 1, s);
+  state_store(edge_state(edges, e), s);
 }
 
 // summaries (APPLY = false) and apply (APPLY = true) over one tile of the sorted pairs
@@ -217,7 +174,7 @@ __global__ void __launch_bounds__(kPriorThreads) prior_tile_kernel(
     const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, const v4u* __restrict__ events, int64_t n,
     uint32_t P, uint32_t* __restrict__ chain, uint32_t* __restrict__ edges,
     const uint32_t* __restrict__ carry, v4u* __restrict__ slot_priors) {
-  __shared__ ScanLds lds;
+  __shared__ PriorScan::Lds lds;
   const int t = threadIdx.x;
   const int64_t tile = blockIdx.x;
   const int64_t lo = tile * kPriorTile;
@@ -227,7 +184,7 @@ __global__ void __launch_bounds__(kPriorThreads) prior_tile_kernel(
     if (!APPLY && t < 2) edges[(2 * tile + t) * kEdgeWords] = kNoKey;
     return;
   }
-  scan_init(lds);
+  PriorScan::init(lds);
   for (int it = 0; it < kPriorIters; ++it) {
     const int64_t i = lo + (int64_t)it * kPriorThreads + t;
     if (lo + (int64_t)it * kPriorThreads >= hi) break;  // uniform over the workgroup
@@ -242,12 +199,12 @@ __global__ void __launch_bounds__(kPriorThreads) prior_tile_kernel(
       if (!first) {
         s = slot_write(vals[i - 1], events, n);
       } else if (APPLY) {
-        s = key == head      ? state_load(carry + (2 * tile) * kEdgeWords + 1)
-            : key == tailkey ? state_load(carry + (2 * tile + 1) * kEdgeWords + 1)
+        s = key == head      ? state_load(edge_state(carry, 2 * tile))
+            : key == tailkey ? state_load(edge_state(carry, 2 * tile + 1))
                              : prior_from_chain(chain + (int64_t)key * kBaseFloats);
       }
     }
-    scan_step(lds, it, key, s);  // the state before element i
+    PriorScan::step(lds, it, key, s);  // the state before element i
     const uint32_t v = has ? vals[i] : 0u;
     if (APPLY) {
       const uint32_t slot = v & kPriorSlotMask;
@@ -301,9 +258,9 @@ __global__ void __launch_bounds__(kPriorThreads) prior_fields_kernel(const v4u* 
 __global__ void __launch_bounds__(kPriorThreads) prior_stitch_kernel(const uint32_t* __restrict__ edges, int64_t E,
                                                                      uint32_t P, uint32_t* __restrict__ chain,
                                                                      uint32_t* __restrict__ carry) {
-  __shared__ ScanLds lds;
+  __shared__ PriorScan::Lds lds;
   const int t = threadIdx.x;
-  scan_init(lds);
+  PriorScan::init(lds);
   const int iters = (int)((E + kPriorThreads - 1) / kPriorThreads);
   for (int it = 0; it < iters; ++it) {
     const int64_t e = (int64_t)it * kPriorThreads + t;
@@ -313,11 +270,11 @@ __global__ void __launch_bounds__(kPriorThreads) prior_stitch_kernel(const uint3
     const bool last = !(e + 1 < E && edges[(e + 1) * kEdgeWords] == key);
     PriorState s = prior_none();
     if (has)
-      s = first ? prior_from_chain(chain + (int64_t)key * kBaseFloats) : state_load(edges + (e - 1) * kEdgeWords + 1);
-    scan_step(lds, it, key, s);  // the state before edge e's stretch
+      s = first ? prior_from_chain(chain + (int64_t)key * kBaseFloats) : state_load(edge_state(edges, e - 1));
+    PriorScan::step(lds, it, key, s);  // the state before edge e's stretch
     if (has) {
-      state_store(carry + e * kEdgeWords + 1, s);
-      if (last) chain_store(chain, key, prior_combine(s, state_load(edges + e * kEdgeWords + 1)));
+      state_store(edge_state(carry, e), s);
+      if (last) chain_store(chain, key, prior_combine(s, state_load(edge_state(edges, e))));
     }
   }
 }

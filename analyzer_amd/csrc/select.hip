@@ -12,8 +12,8 @@
 //          iteration: the record is loaded with the widest vector loads its size allows
 //          (16 / 24 / 32 / 40 / 48 B for K = 1..5: 16-B loads, 8-B loads for K = 2, 4),
 //          the per-match hit mask popcounted and summed over the tile -> counts[tile]
-//   scan   one workgroup: exclusive scan of the tile counts -> offsets[tile], the total
-//          in offsets[tiles]
+//   scan   launch_tile_offsets: exclusive scan of the tile counts -> offsets[tile], the
+//          total in offsets[tiles]
 //   emit   the same tile walk; a hit's index is offsets[tile] + the hits of the tile's
 //          earlier iterations + the waves before this one (LDS) + a shuffle scan over
 //          the lanes' counts; each hit is three 16-B stores.  A tile without hits ends
@@ -26,6 +26,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "record_dev.h"
+#include "scan_dev.h"
 #include "select_core.h"
 
 namespace ana {
@@ -33,7 +34,6 @@ namespace ana {
 namespace {
 
 constexpr int kSelectThreads = 256;
-constexpr int kSelectWaves = kSelectThreads / 64;
 constexpr int kSelectIters = kSelectTile / kSelectThreads;
 static_assert(kSelectTile % kSelectThreads == 0, "a tile is a whole number of iterations");
 
@@ -69,49 +69,7 @@ __global__ void __launch_bounds__(kSelectThreads) select_count_kernel(const int3
     uint32_t st;
     n += (uint32_t)__popc(match_mask<K>(rec, rows, W, M, m0 + (int64_t)i * kSelectThreads, P, bitmap, r, st));
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o, 64);
-  __shared__ uint32_t wsum[kSelectWaves];
-  if ((t & 63) == 0) wsum[t >> 6] = n;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t s = 0u;
-#pragma unroll
-    for (int w = 0; w < kSelectWaves; ++w) s += wsum[w];
-    counts[blockIdx.x] = s;
-  }
-}
-
-// one workgroup: lane l owns the tiles [l * per, (l + 1) * per)
-__global__ void __launch_bounds__(kSelectThreads) select_scan_kernel(const uint32_t* __restrict__ counts, int64_t tiles,
-                                                                     int64_t* __restrict__ offsets) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t per = (tiles + kSelectThreads - 1) / kSelectThreads;
-  const int64_t lo = (int64_t)t * per < tiles ? (int64_t)t * per : tiles;
-  const int64_t hi = lo + per < tiles ? lo + per : tiles;
-  int64_t own = 0;
-  for (int64_t i = lo; i < hi; ++i) own += counts[i];
-  int64_t incl = own;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t v = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += v;
-  }
-  __shared__ int64_t wsum[kSelectWaves];
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int64_t before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kSelectWaves; ++w) {
-    before += w < wave ? wsum[w] : 0;
-    total += wsum[w];
-  }
-  int64_t run = before + incl - own;
-  for (int64_t i = lo; i < hi; ++i) {
-    offsets[i] = run;
-    run += counts[i];
-  }
-  if (t == 0) offsets[tiles] = total;
+  block_sum_store<kSelectThreads>(n, counts + blockIdx.x);
 }
 
 template <int K>
@@ -122,12 +80,10 @@ __global__ void __launch_bounds__(kSelectThreads) select_emit_kernel(const int32
                                                                      const int64_t* __restrict__ offsets,
                                                                      int32_t* __restrict__ hits, int64_t nhits) {
   constexpr int S = 2 * K;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, lane = t & 63;
   int64_t run = offsets[blockIdx.x];
   if (offsets[blockIdx.x + 1] == run) return;  // no hit in this tile (uniform over the workgroup)
   const int64_t m0 = (int64_t)blockIdx.x * kSelectTile + t;
-  // per-wave sums, double-buffered over the iterations: one barrier per iteration
-  __shared__ int wsum[2][kSelectWaves];
   for (int i = 0; i < kSelectIters; ++i) {
     const int64_t m = m0 + (int64_t)i * kSelectThreads;
     int32_t r[S + 2];
@@ -140,15 +96,8 @@ __global__ void __launch_bounds__(kSelectThreads) select_emit_kernel(const int32
       const int v = __shfl_up(incl, o, 64);
       if (lane >= o) incl += v;
     }
-    if (lane == 63) wsum[i & 1][wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kSelectWaves; ++w) {
-      const int s = wsum[i & 1][w];
-      before += w < wave ? s : 0;
-      total += s;
-    }
+    int total;
+    const int before = block_offset<kSelectThreads>(i, incl, total);
     int64_t idx = run + before + incl - own;
     run += total;
     if (mask) {
@@ -189,8 +138,7 @@ int launch_records_select_count(int K, const int32_t* rec, const float* rows, in
                          rec, rw, W, M, P, bitmap, counts);
     });
   }
-  hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(kSelectThreads), 0, s, counts, tiles, offsets);
-  return (int)hipGetLastError();
+  return launch_tile_offsets(counts, tiles, offsets, s);
 }
 
 int launch_records_select_emit(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base,

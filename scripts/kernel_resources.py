@@ -1,16 +1,21 @@
 """Per-kernel VGPRs / spills / LDS / occupancy of a HIP source (hipcc
 -Rpass-analysis=kernel-resource-usage): python scripts/kernel_resources.py <src.hip> [name-substring]
-[extra hipcc flags...].  Compiles to /tmp; prints one line per kernel."""
+[extra hipcc flags...].  Compiles to /tmp with the flags the production build uses for that file
+(analyzer_amd/build_ext.py HIP_FLAGS); prints one line per kernel."""
+import os
 import re
 import subprocess
 import sys
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from analyzer_amd import build_ext  # noqa: E402
+
 src = sys.argv[1]
 sub = sys.argv[2] if len(sys.argv) > 2 else ""
 extra = sys.argv[3:]
-cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Ianalyzer_amd/csrc", "-fapprox-func",
-       "-freciprocal-math", "-fno-signed-zeros", "-Rpass-analysis=kernel-resource-usage", "-c", src,
-       "-o", "/tmp/kernel_resources.o"] + extra
+cmd = ["hipcc", "--offload-arch=" + build_ext.ARCH, "-O3", "-std=c++17", "-fPIC", "-I" + str(build_ext.CSRC)]
+cmd += build_ext.HIP_FLAGS.get(os.path.basename(src), [])
+cmd += ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/tmp/kernel_resources.o"] + extra
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur, rows = None, []
 for line in out.splitlines():

@@ -142,6 +142,13 @@ def case(name):
         for edge in range(TILE, live, TILE):  # a player's run straddles every tile edge
             assert keys[edge - 1] == keys[edge], (name, edge)
         return chain, rec, rows
+    if kind == "stitch":  # 129 tiles, 258 edges: the stitch kernel runs a second iteration
+        chain, rec, rows = synthetic(5, 52_429, 37, seed=99)
+        keys = np.sort(live_keys(rec, 37))
+        assert len(keys) == 524_290 and 2 * -(-len(keys) // TILE) == 258
+        # edge 255 ends tile 127, edge 256 begins tile 128: one player's run crosses the iterations
+        assert keys[128 * TILE - 1] == keys[128 * TILE]
+        return chain, rec, rows
     if kind == "every":  # one player in every match across three tiles: a whole tile is one key
         M = 3 * TILE + 5
         ids = np.stack([np.zeros(M, dtype=np.int64), 1 + np.arange(M) % 5], axis=1)
@@ -182,6 +189,7 @@ def live_keys(rec, P):
 FEW_CASES = ["few:%d" % K for K in KS]
 TILE_CASES = ["tile:%d:%d" % (K, n) for K in KS for n in (TILE - 1, TILE, TILE + 1, 2 * TILE + 3)]
 LONG_CASES = ["every", "alternate", "twins"]
+DEVICE_LONG_CASES = LONG_CASES + ["stitch"]  # 524,290 slots: the oracle alone takes seconds, so on the device only
 OTHER_CASES = ["sparse", "split"]
 
 

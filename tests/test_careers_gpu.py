@@ -24,7 +24,7 @@ def test_tile_edges(gpu_device, name):
     C.check_case(name, gpu_device)
 
 
-@pytest.mark.parametrize("name", C.LONG_CASES)
+@pytest.mark.parametrize("name", C.DEVICE_LONG_CASES)
 def test_long_runs(gpu_device, name):
     C.check_case(name, gpu_device)
 
@@ -69,7 +69,7 @@ def test_columns_and_lookup(gpu_device):
     C.check_lookup(gpu_device)
 
 
-@pytest.mark.parametrize("name", ["alias", "few:3", "tile:3:%d" % (2 * C.TILE + 3), "mixed"])
+@pytest.mark.parametrize("name", ["alias", "few:3", "tile:3:%d" % (2 * C.TILE + 3), "mixed", "stitch"])
 def test_same_bits_on_every_run(gpu_device, name):
     first = C.run(name, gpu_device).table.cpu()
     assert torch.equal(C.run(name, gpu_device).table.cpu(), first)

@@ -29,7 +29,7 @@ def test_tile_edges(gpu_device, name):
     C.check_priors(name, gpu_device)
 
 
-@pytest.mark.parametrize("name", C.LONG_CASES)
+@pytest.mark.parametrize("name", C.DEVICE_LONG_CASES)
 def test_long_runs(gpu_device, name):
     C.check_priors(name, gpu_device)
 
