@@ -241,9 +241,8 @@ class EngineConfig:
     # (csrc/telemetry.hip, kernels.hip, radix_sort.hip) -- experiments, not tuning
     NATIVE_KNOBS = {
         "ANA_TELE_IMPL": "telemetry aggregation: 1 one-hot MFMA GEMM (default), 0 LDS atomics",
-        "ANA_SCHED_SMALL": "micro-batch schedule: hash lists (default) or bitonic sort",
-        "ANA_SORT_RB / ANA_SORT_NT": "radix-sort tile rows / non-temporal loads (tuning)",
-        "ANA_SCHED_RUNS": "last schedule pass: run-end table (1, default) or digit offsets + fix-up (0)",
+        "ANA_SORT_NT": "0 / 2: non-temporal loads of the schedule sort (test override of what the window "
+                       "pipeline passes)",
         "ANA_SCHED_CHAIN": "schedule of <= 2^20 players: one partition + per-bucket LDS chain pass (1; default "
                            "where a bucket is short enough) or three LSD passes (0)",
     }

@@ -267,6 +267,8 @@ void schedule(Tensor rec, int64_t K, int64_t num_players, Tensor link, Tensor de
   check_schedule(link, deps, M, K, dev);
   TORCH_CHECK(num_players >= 1 && num_players < 0x7fffffffLL, "num_players out of range");
   TORCH_CHECK(M * 2 * K <= ana::kMaxSlots, "more than 2^28 slots in one window (split the stream)");
+  TORCH_CHECK(sort_nt == -1 || sort_nt == 0 || sort_nt == 2,
+              "sort_nt must be 0 (plain loads), 2 (non-temporal loads) or -1 (ANA_SORT_NT or plain), got ", sort_nt);
   if (dev.is_cuda()) {
     check(workspace, "workspace", torch::kUInt8, dev);
     check(ctrl, "ctrl", torch::kInt32, dev);

@@ -166,7 +166,8 @@ int launch_pair_emit(const uint32_t* a, const uint32_t* b, const uint32_t* vals,
 
 // Stable LSD radix sort of (key, value) pairs on the low ``bits`` key bits
 // (radix_sort.hip).  Ping-pongs between the two buffer pairs; *result_in_alt
-// says which holds the result.  ws: radix_sort_workspace_bytes(n) bytes.
+// says which holds the result.  ws: radix_sort_workspace_bytes(n) bytes (256 counts per
+// 8192-element tile and the 256 digit totals; the schedule's run table reuses them).
 size_t radix_sort_workspace_bytes(int64_t n);
 int launch_radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt,
                             int64_t n, int bits, void* ws, int* result_in_alt, hipStream_t s);
@@ -176,9 +177,10 @@ int launch_radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, 
 // ws: radix_sort_workspace_bytes(M * 2K) bytes; ka..vb: M * 2K words each.
 // deps [M] (zeroed by the first kernel), ctrl[0..nz) (zeroed), epoch_bump (+1): the
 // schedule's fill work, folded into that kernel (null / 0: skipped).  sort_nt (ANA_SORT_NT wins):
-// non-temporal accesses of the sort, 0 none, 1 all, 2 loads only -- what a caller asks for whose
-// prepass runs beside the executor, so with >= 1 the chain path also writes its links as whole
-// lines (sched_unpartition), which costs the executor less and the prepass itself more
+// non-temporal loads of the sort, 0 none, 2 every pass's input (-1: ANA_SORT_NT or none) -- 2 is
+// what a caller asks for whose prepass runs beside the executor, so with it the chain path also
+// writes its links as whole lines (sched_unpartition), which costs the executor less and the
+// prepass itself more.  Any other value: hipErrorInvalidValue, nothing launched.
 int launch_sched_sort(int K, const int32_t* rec, int64_t M, uint32_t num_players, uint32_t* ka,
                       uint32_t* va, uint32_t* kb, uint32_t* vb, void* ws, uint32_t* link,
                       hipStream_t s, int32_t* deps = nullptr, uint32_t* ctrl = nullptr, int nz = 0,
@@ -195,6 +197,8 @@ int launch_levels(int K, const int32_t* rec, const uint32_t* link, int32_t* deps
 //       match is ready when its counter reaches the number of its players with
 //       kLinkHasPred, which the executor reads from the links)
 // overflow: zeroed (reserved for schedule error reporting)
+// Up to 8192 slots one workgroup links the batch through LDS hash lists (sched_hash_kernel);
+// larger windows take launch_sched_sort, which sort_nt is for.
 int launch_schedule(int K, const int32_t* rec, int64_t M, int64_t P, uint32_t* link,
                     int32_t* deps, void* ws, size_t ws_bytes, uint32_t* overflow, hipStream_t s,
                     bool zero_ctrl = false, int32_t* epoch_bump = nullptr, int sort_nt = -1);

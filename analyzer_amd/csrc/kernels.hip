@@ -18,6 +18,7 @@
 #include "gen_core.h"
 #include "kernels.h"
 #include "rate_core.h"
+#include "record_dev.h"
 
 namespace ana {
 
@@ -177,114 +178,21 @@ size_t schedule_workspace_bytes(int64_t nslots, int64_t num_players) {
 
 // Micro-batch schedule (a worker batch of <= kSmallSched slots, e.g. 500 3v3 or
 // 5v5 matches): ONE workgroup keys the slots (player, or past the last player
-// for matches that touch no state), sorts (key << 32 | slot) -- stable by slot,
-// like the radix path --, writes every slot's link from its sorted neighbours
-// and zeroes the completion counters: one dispatch instead of the radix path's
-// ~12, which are launch-bound at this size.  The bitonic network keeps E
-// consecutive elements per thread in registers: exchanges closer than E run in
-// registers, closer than 64 E (one wave) through lane shuffles, and only the
-// few wider ones through LDS with a barrier.
+// for matches that touch no state), writes every slot's link and zeroes the
+// completion counters: one dispatch instead of the radix path's ~12, which are
+// launch-bound at this size.  It does not sort.  A link only needs, per slot, the
+// next slot of the same player and whether an earlier one exists -- not a total
+// order.  So: key every slot into LDS, push each keyed slot onto an LDS list per
+// hash bucket (one ds atomic swap: the lists are unordered), then every slot walks
+// its bucket's list and keeps the smallest later slot with its key (its successor)
+// and whether any earlier slot has it (its predecessor flag) -- the same links as
+// the radix path's stable sort.  4096 buckets for <= 8192 slots: lists of ~1-2
+// slots and three barriers.  (A one-workgroup bitonic sort of (key << 32 | slot),
+// ~80 dependent exchange stages, took 38.6 against 5.3 us per 3v3 batch,
+// profiles/microbatch_hash_sched.log.)
+// LDS: 16 KB heads + 16 KB u16 list links + 32 KB keys.
 constexpr int kSmallSched = 8192;
 constexpr int kSmallThreads = 1024;
-
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-template <int K, int E>
-__global__ void __launch_bounds__(kSmallThreads)
-sched_small_kernel(const int32_t* __restrict__ rec, int64_t M, uint32_t kend, uint32_t* __restrict__ link,
-                   int32_t* __restrict__ deps, uint32_t* __restrict__ overflow) {
-  constexpr int S = 2 * K, R = S + 2;
-  constexpr int NP = kSmallThreads * E;  // padded sort size
-  __shared__ uint64_t kv[NP];
-  const int tid = threadIdx.x;
-  const int n = (int)(M * S);
-  for (int m = tid; m < (int)M; m += kSmallThreads) {
-    int32_t r[R];
-#pragma unroll
-    for (int k = 0; k < R; ++k) r[k] = rec[(int64_t)m * R + k];
-    const bool rates = early_status<K>(r, (int64_t)kend) == kRated;
-    const uint32_t m0 = (uint32_t)r[S];
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-      const int pos = j < K ? j : j - K;
-      const bool in_roster = pos < (j < K ? meta_n0(m0) : meta_n1(m0));
-      const uint32_t key = rates && in_roster ? (uint32_t)r[j] : kend;
-      kv[m * S + j] = ((uint64_t)key << 32) | (uint32_t)(m * S + j);
-    }
-    deps[m] = 0;
-  }
-  for (int i = n + tid; i < NP; i += kSmallThreads) kv[i] = ~0ull;
-  if (tid == 0) *overflow = 0u;
-  __syncthreads();
-  uint64_t x[E];
-#pragma unroll
-  for (int q = 0; q < E; ++q) x[q] = kv[tid * E + q];
-  for (int k = 2; k <= NP; k <<= 1) {
-    for (int j = k >> 1; j >= E; j >>= 1) {
-      const bool wave = j < 64 * E;
-      if (!wave) {  // partner in another wave: exchange through LDS
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < E; ++q) kv[tid * E + q] = x[q];
-        __syncthreads();
-      }
-#pragma unroll
-      for (int q = 0; q < E; ++q) {  // partner: same register of lane ^ j / E, or LDS
-        const int i = tid * E + q;
-        const uint64_t y = wave ? shfl_xor64(x[q], j / E) : kv[i ^ j];
-        const bool lower = (i & j) == 0, asc = (i & k) == 0;
-        const uint64_t lo = x[q] < y ? x[q] : y, hi = x[q] < y ? y : x[q];
-        x[q] = lower == asc ? lo : hi;
-      }
-    }
-    // partners in this thread's registers (compile-time indices: no scratch)
-#pragma unroll
-    for (int jj = E / 2; jj > 0; jj >>= 1) {
-      if (jj >= k) continue;
-#pragma unroll
-      for (int q = 0; q < E; ++q) {
-        const int qp = q ^ jj;
-        if (qp > q) {
-          const int i = tid * E + q;
-          const uint64_t a = x[q], b = x[qp];
-          if ((a > b) == ((i & k) == 0)) {
-            x[q] = b;
-            x[qp] = a;
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < E; ++q) kv[tid * E + q] = x[q];
-  __syncthreads();
-  for (int p = tid; p < n; p += kSmallThreads) {
-    const uint64_t v64 = kv[p];
-    const uint32_t key = (uint32_t)(v64 >> 32), v = (uint32_t)v64;
-    uint32_t w = kNoMatch;
-    if (key < kend) {
-      if (p + 1 < n && (uint32_t)(kv[p + 1] >> 32) == key) w = (uint32_t)kv[p + 1] / (uint32_t)S;
-      if (p > 0 && (uint32_t)(kv[p - 1] >> 32) == key) w |= kLinkHasPred;
-    }
-    link[v] = w;
-  }
-}
-
-// Micro-batch schedule without a sort (default; ANA_SCHED_SMALL=bitonic selects the
-// kernel above for A/B).  A link only needs, per slot, the next slot of the same
-// player and whether an earlier one exists -- not a total order.  So: key every
-// slot into LDS, push each keyed slot onto an LDS list per hash bucket (one
-// ds atomic swap: the lists are unordered), then every slot walks its bucket's
-// list and keeps the smallest later slot with its key (its successor) and
-// whether any earlier slot has it (its predecessor flag) -- the same links as
-// the stable sort.  4096 buckets for <= 8192 slots: lists of ~1-2 slots, three
-// barriers instead of the bitonic network's ~80 dependent exchange stages.
-// LDS: 16 KB heads + 16 KB u16 list links + 32 KB keys.
 constexpr int kHashBuckets = 4096;
 
 template <int K>
@@ -300,26 +208,10 @@ sched_hash_kernel(const int32_t* __restrict__ rec, int64_t M, uint32_t kend, uin
   const int n = (int)(M * S);
   for (int b = tid; b < kHashBuckets; b += kSmallThreads) head[b] = 0xffffffffu;
   for (int m = tid; m < (int)M; m += kSmallThreads) {
-    int32_t r[R];
-    const int32_t* src = rec + (int64_t)m * R;
-    if constexpr (R % 4 == 0) {
+    uint32_t key[S];
+    sched_slot_keys<K>(rec + (int64_t)m * R, (int64_t)kend, kend, key);
 #pragma unroll
-      for (int k = 0; k < R / 4; ++k) {
-        const int4 v = reinterpret_cast<const int4*>(src)[k];
-        r[4 * k] = v.x; r[4 * k + 1] = v.y; r[4 * k + 2] = v.z; r[4 * k + 3] = v.w;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < R; ++k) r[k] = src[k];
-    }
-    const bool rates = early_status<K>(r, (int64_t)kend) == kRated;
-    const uint32_t m0 = (uint32_t)r[S];
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-      const int pos = j < K ? j : j - K;
-      const bool in_roster = pos < (j < K ? meta_n0(m0) : meta_n1(m0));
-      skey[m * S + j] = rates && in_roster ? (uint32_t)r[j] : kend;
-    }
+    for (int j = 0; j < S; ++j) skey[m * S + j] = key[j];
     deps[m] = 0;
   }
   if (tid < nz) overflow[tid] = 0u;
@@ -362,26 +254,11 @@ int launch_schedule(int K, const int32_t* rec, int64_t M, int64_t P, uint32_t* l
   if (K < 1 || K > kMaxTeamSize) return (int)hipErrorInvalidValue;
   const int64_t n = M * 2 * K;
   if (n > 0 && n <= kSmallSched && P < 0x7fffffffLL) {
-    const int e = n <= 2048 ? 2 : n <= 4096 ? 4 : 8;  // elements per thread
-    const char* small_e = getenv("ANA_SCHED_SMALL");  // per schedule (A/B in one process)
-    const bool bitonic = small_e && small_e[0] == 'b';
     with_team_size(K, [&](auto k) {
       constexpr int kK = decltype(k)::value;
-      if (!bitonic)
-        hipLaunchKernelGGL((sched_hash_kernel<kK>), dim3(1), dim3(kSmallThreads), 0, s, rec, M, (uint32_t)P, link,
-                           deps, overflow, nz, epoch_bump);
-      else if (e == 2)
-        hipLaunchKernelGGL((sched_small_kernel<kK, 2>), dim3(1), dim3(kSmallThreads), 0, s, rec, M, (uint32_t)P,
-                           link, deps, overflow);
-      else if (e == 4)
-        hipLaunchKernelGGL((sched_small_kernel<kK, 4>), dim3(1), dim3(kSmallThreads), 0, s, rec, M, (uint32_t)P,
-                           link, deps, overflow);
-      else
-        hipLaunchKernelGGL((sched_small_kernel<kK, 8>), dim3(1), dim3(kSmallThreads), 0, s, rec, M, (uint32_t)P,
-                           link, deps, overflow);
+      hipLaunchKernelGGL((sched_hash_kernel<kK>), dim3(1), dim3(kSmallThreads), 0, s, rec, M, (uint32_t)P, link,
+                         deps, overflow, nz, epoch_bump);
     });
-    if (bitonic && zero_ctrl) ANA_HIP_CHECK(hipMemsetAsync(overflow, 0, 64, s));
-    if (bitonic && epoch_bump) hipLaunchKernelGGL(epoch_bump_kernel, dim3(1), dim3(1), 0, s, epoch_bump);
     return (int)hipGetLastError();
   }
   if (n <= 0) {

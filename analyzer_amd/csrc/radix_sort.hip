@@ -13,31 +13,41 @@
 //   downsweep per tile: stable rank in wave order (8 ballots -> peer mask),
 //             wave prefixes in LDS, local scatter into an LDS-sorted tile,
 //             then coalesced runs to the global digit offsets.
-// 8192-element tiles (512 threads x 16: the per-(tile, digit) runs the downsweeps write
-// average 32 elements, whole 128-B lines; 4096-element tiles measured 0.03-0.04 ms slower
-// per 10M 3v3 prepass, profiles/r3/sort_tile_8192.log); 8-bit digits (10-bit ones for the
-// schedule are an opt-in experiment, ANA_SORT_RB: fewer passes but measured slower).
+// 8192-element tiles (512 threads x 16) and 8-bit digits: the per-(tile, digit) runs the
+// downsweeps write average 32 elements, whole 128-B lines.  Measured and not taken:
+//   4096-element tiles (256 threads): 0.03-0.04 ms slower per 10M 3v3 prepass
+//     (profiles/r3/sort_tile_8192.log);
+//   10-bit digits for the schedule (two passes for <= 2^20 players): 3.11 against 1.76 ms per
+//     prepass -- 1024 runs of ~4 elements per tile scatter the writes, 56 KB of LDS halve the
+//     link pass's occupancy, the fix-up has four times the runs
+//     (profiles/r3/prepass_rb8_vs_rb10.txt);
+//   non-temporal stores: see ld32.
 //
 // The schedule prepass (launch_sched_sort) fuses both ends: pass 0 computes its
 // keys from the match records, and the last pass writes each slot's link from
 // its LDS neighbours instead of the sorted pairs (only run-boundary pairs go out,
 // for the fix-up).  For 10M 3v3 matches that drops a 480-MB key/value write, the
-// re-reads of it and a separate 720-MB link pass.
+// re-reads of it and a separate 720-MB link pass.  The fix-up of a last pass over at most
+// 32 digits (1M players: bits 16..19) works from a [tile][digit] table of run ends, which
+// needs no upsweep / rowscan in front of that pass (1.63 against 1.78 ms per prepass,
+// profiles/r3/sched_run_table.log); a last pass over more digits (10M players) scatters
+// its boundary pairs to their digit offsets for sched_fixup.
 //
-// Rosters of <= 2^20 players (round 7) need only the first of those passes: one stable
+// Rosters of <= 2^20 players need only the first of those passes: one stable
 // partition by the key bits above the low 12, then sched_chain -- one workgroup per bucket
 // sorts its tiles in LDS and chains each player's slots through a last-occurrence table
 // (4 launches and ~1.84 GB per 10M 3v3 window instead of 9 and ~3.0 GB; 1.22-1.25 ms alone
 // against 1.60-1.64, the config 2 step 0.10-0.12 ms shorter, profiles/r7/sched_chain_ab.log).
-// Larger rosters keep the three LSD passes; ANA_SCHED_CHAIN=0 selects them for A/B.
+// Larger rosters, and windows whose buckets would be long (launch_sched_sort), take the
+// three LSD passes; ANA_SCHED_CHAIN=1 / 0 forces either, which is how small tests reach both.
 //
-// Beside the executor the links of that path leave as whole lines (round 8; a prepass with nothing
-// beside it keeps the direct stores, see sched_sort_k).  sched_chain writes link[slot] there:
+// Beside the executor the links of the chain path leave as whole lines (a prepass with nothing
+// beside it keeps the direct stores, see sched_sort_k).  Direct, sched_chain writes link[slot]:
 // 60M random 4-B stores per window, one fabric write request each, beside an executor whose time
-// is the latency of its own requests.  The new variant writes each link at the slot's position in its
-// bucket, in place over the bucket's keys and one tile late through an LDS buffer, so that a link
-// resolved by the next tile still leaves inside a coalesced run; 6.2 % of the links (deferred
-// past the next tile, or to the final flush) remain single stores.  sched_unpartition, one
+// is the latency of its own requests.  The whole-lines variant writes each link at the slot's
+// position in its bucket, in place over the bucket's keys and one tile late through an LDS buffer,
+// so that a link resolved by the next tile still leaves inside a coalesced run; 6.2 % of the links
+// (deferred past the next tile, or to the final flush) remain single stores.  sched_unpartition, one
 // workgroup per input tile, then reads the tile's 256 runs back through the partition's own
 // offset table and writes link[] in slot order with 16-B stores.  5 launches and ~2.56 GB per
 // window, but 10.3M write requests from the two kernels instead of 58.8M: alone the prepass is
@@ -49,20 +59,19 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "record_dev.h"
 
 namespace ana {
 
 namespace {
 
-#ifndef ANA_SORT_THREADS
-#define ANA_SORT_THREADS 512  // threads per tile (x 16 items = 8192 elements; 256: 4096, A/B)
-#endif
-constexpr int kThreads = ANA_SORT_THREADS;
+constexpr int kThreads = 512;  // threads per tile (x 16 items = 8192 elements)
 constexpr int kWaves = kThreads / 64;
 constexpr int kItems = 16;
 constexpr int kTile = kThreads * kItems;
-constexpr int kRadix = 256;      // 8-bit digits (generic sort; schedule keys > 20 bits)
-constexpr int kRadixMax = 1024;  // 10-bit digits: the schedule of <= 2^20 players in 2 passes
+constexpr int kRadixBits = 8;
+constexpr int kRadix = 1 << kRadixBits;  // digits per pass: at most one per thread in the scans
+static_assert(kRadix <= kThreads, "one digit per thread");
 
 // Tile of this workgroup.  Workgroups go round-robin over the 8 XCDs; giving
 // each XCD a contiguous range of tiles puts the digit runs that consecutive
@@ -73,21 +82,16 @@ __device__ __forceinline__ int64_t xcd_tile(int64_t tiles) {
   return x * q + (x < r ? x : r) + (i >> 3);
 }
 
-// NT: streaming (non-temporal) accesses for the sort's key/value/link traffic, so
-// a prepass that co-runs with the dataflow executor does not evict the roster
-// the executor keeps in the Infinity Cache.  Opt-in (ANA_SORT_NT=1): measured on
-// MI355X the prepass slows 1.75 -> 4.35 ms (the digit runs lose L2 write
-// combining) and the bench step 8.1 -> 9.2 ms.  ANA_SORT_NT=2: non-temporal loads
-// only (each pass streams its input once; the scattered stores keep L2 combining).
-template <int NT>
+// NT: streaming (non-temporal) loads of the sort's key / value / link input, so a prepass
+// that co-runs with the dataflow executor evicts less of the roster the executor keeps in
+// the Infinity Cache (each pass reads its input once).  Stores stay plain: the digit runs
+// need L2 write combining -- non-temporal stores as well measured 4.35 against 1.75 ms per
+// prepass and 9.2 against 8.1 ms per bench step (re-checked: config 3 17.0 against 14.9 ms,
+// config 5 14.1 against 10.9, profiles/r6/tail_points.log).
+template <bool NT>
 __device__ __forceinline__ uint32_t ld32(const uint32_t* p) {
-  if constexpr (NT >= 1) return __builtin_nontemporal_load(p);
+  if constexpr (NT) return __builtin_nontemporal_load(p);
   else return *p;
-}
-template <int NT>
-__device__ __forceinline__ void st32(uint32_t* p, uint32_t v) {
-  if constexpr (NT == 1) __builtin_nontemporal_store(v, p);
-  else *p = v;
 }
 
 // exclusive scan of one value per thread over a 256-thread block
@@ -126,26 +130,12 @@ __device__ __forceinline__ void decode_tile_keys(const int32_t* __restrict__ rec
   const uint32_t hi = (uint32_t)(base + kTile < n ? base + kTile : n);
   const uint32_t m_lo = lo / S, m_hi = (hi + S - 1) / S;
   for (uint32_t m = m_lo + threadIdx.x; m < m_hi; m += kThreads) {
-    const int32_t* src = rec + (int64_t)m * R;
-    int32_t r[R];
-    if constexpr (R % 4 == 0) {
-#pragma unroll
-      for (int k = 0; k < R / 4; ++k) {
-        const int4 v = reinterpret_cast<const int4*>(src)[k];
-        r[4 * k] = v.x; r[4 * k + 1] = v.y; r[4 * k + 2] = v.z; r[4 * k + 3] = v.w;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < R; ++k) r[k] = src[k];
-    }
-    const bool rates = early_status<KS>(r, (int64_t)kend) == kRated;
-    const uint32_t m0 = (uint32_t)r[S];
+    uint32_t key[S];
+    sched_slot_keys<KS>(rec + (int64_t)m * R, (int64_t)kend, knone, key);
 #pragma unroll
     for (int j = 0; j < S; ++j) {
       const uint32_t slot = m * S + j;
-      const int pos = j < KS ? j : j - KS;
-      const bool in_roster = pos < (j < KS ? meta_n0(m0) : meta_n1(m0));
-      if (slot >= lo && slot < hi) lk[slot - lo] = rates && in_roster ? (uint32_t)r[j] : knone;
+      if (slot >= lo && slot < hi) lk[slot - lo] = key[j];
     }
   }
 }
@@ -161,16 +151,15 @@ struct SchedInit {
 };
 
 // KS > 0: keys from the match stream (decode_tile_keys), and the SchedInit duties.
-template <int KS, int RB = 8, int NT = 0>
+template <int KS, bool NT = false>
 __global__ void __launch_bounds__(kThreads)
 radix_upsweep(const uint32_t* __restrict__ keys, const int32_t* __restrict__ rec, uint32_t kend,
               int64_t n, int shift, uint32_t* __restrict__ counts, int64_t tiles, SchedInit init = {},
               uint32_t knone = 0u) {
-  constexpr int kR = 1 << RB;
-  __shared__ uint32_t hist[kWaves][kR];
+  __shared__ uint32_t hist[kWaves][kRadix];
   __shared__ uint32_t lkeys[KS > 0 ? kTile : 1];
   const int tid = threadIdx.x, wv = tid >> 6;
-  for (int i = tid; i < kWaves * kR; i += kThreads) (&hist[0][0])[i] = 0u;
+  for (int i = tid; i < kWaves * kRadix; i += kThreads) (&hist[0][0])[i] = 0u;
   const int64_t tile = xcd_tile(tiles);
   const int64_t base = tile * kTile;
   if constexpr (KS > 0) {
@@ -191,34 +180,17 @@ radix_upsweep(const uint32_t* __restrict__ keys, const int32_t* __restrict__ rec
     const int64_t idx = base + k * kThreads + tid;
     if (idx < n) {
       const uint32_t key = KS > 0 ? lkeys[k * kThreads + tid] : ld32<NT>(keys + idx);
-      atomicAdd(&hist[wv][(key >> shift) & (kR - 1)], 1u);
+      atomicAdd(&hist[wv][(key >> shift) & (kRadix - 1)], 1u);
     }
   }
   __syncthreads();
 #pragma unroll
-  for (int d = tid; d < kR; d += kThreads) {
+  for (int d = tid; d < kRadix; d += kThreads) {
     uint32_t c = 0;
 #pragma unroll
     for (int w = 0; w < kWaves; ++w) c += hist[w][d];
     counts[(int64_t)d * tiles + tile] = c;
   }
-}
-
-// exclusive scan over kR per-digit values held as DPT = kR / kThreads consecutive
-// digits per thread (v[] in, prefixes out); *total = the sum of all
-template <int DPT>
-__device__ __forceinline__ void digits_exclusive_scan(uint32_t (&v)[DPT], uint32_t* wsum,
-                                                      uint32_t* total) {
-  uint32_t s = 0;
-#pragma unroll
-  for (int j = 0; j < DPT; ++j) {
-    const uint32_t x = v[j];
-    v[j] = s;
-    s += x;
-  }
-  const uint32_t before = block_exclusive_scan(s, wsum, total);
-#pragma unroll
-  for (int j = 0; j < DPT; ++j) v[j] += before;
 }
 
 // One workgroup per digit: counts[d][*] <- exclusive prefix over tiles; totals[d] <- row sum.
@@ -265,7 +237,7 @@ constexpr uint32_t kRunEmpty = 0xffffffffu;
 // [tile][nd] RunEnds table instead of their global sorted positions, so this pass
 // needs no digit offsets -- no upsweep / rowscan in front of it -- and sched_runs_fixup
 // links each run to the nearest non-empty run of its digit in an earlier tile.
-template <int KS, bool LINK, int RB = 8, int NT = 0>
+template <int KS, bool LINK, bool NT = false>
 __global__ void __launch_bounds__(kThreads)
 radix_downsweep(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
                 const int32_t* __restrict__ rec, uint32_t kend,
@@ -274,28 +246,20 @@ radix_downsweep(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ v
                 int64_t tiles, int slots_per_match, uint32_t* __restrict__ link,
                 uint32_t vlo = 0u, uint32_t vhi = 0xffffffffu, int bounds = 1,
                 RunEnds* __restrict__ bnd = nullptr, int nd = 0, uint32_t knone = 0u) {
-  constexpr int kR = 1 << RB;
-  constexpr int DPT = kR >= kThreads ? kR / kThreads : 1;  // digits per thread in the scans
-  static_assert(kR % kThreads == 0 || kThreads % kR == 0, "radix and block must divide");
   __shared__ uint32_t skey[kTile];
   __shared__ uint32_t sval[kTile];
-  __shared__ uint32_t wcnt[kWaves][kR];
-  __shared__ uint32_t tstart[kR];
-  __shared__ uint32_t gstart[kR];
+  __shared__ uint32_t wcnt[kWaves][kRadix];
+  __shared__ uint32_t tstart[kRadix];
+  __shared__ uint32_t gstart[kRadix];
   __shared__ uint32_t wsum[kWaves];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int64_t tile = xcd_tile(tiles);
   const int64_t base = tile * kTile;
-  for (int i = tid; i < kWaves * kR; i += kThreads) (&wcnt[0][0])[i] = 0u;
+  for (int i = tid; i < kWaves * kRadix; i += kThreads) (&wcnt[0][0])[i] = 0u;
   const bool local_ends = LINK && bnd != nullptr;  // uniform: no global digit offsets needed
   if (!local_ends) {  // global start of each digit for this tile
-    uint32_t v[DPT];
-#pragma unroll
-    for (int j = 0; j < DPT; ++j) v[j] = tid * DPT + j < kR ? totals[tid * DPT + j] : 0u;
-    digits_exclusive_scan<DPT>(v, wsum, nullptr);
-#pragma unroll
-    for (int j = 0; j < DPT; ++j)
-      if (tid * DPT + j < kR) gstart[tid * DPT + j] = v[j] + counts[(int64_t)(tid * DPT + j) * tiles + tile];
+    const uint32_t below = block_exclusive_scan(tid < kRadix ? totals[tid] : 0u, wsum, nullptr);
+    if (tid < kRadix) gstart[tid] = below + counts[(int64_t)tid * tiles + tile];
   }
   if constexpr (KS > 0)  // sval: scratch until the scatter
     decode_tile_keys<KS>(rec, kend, base, n, sval, knone ? knone : kend);
@@ -317,10 +281,10 @@ radix_downsweep(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ v
   }
 #pragma unroll
   for (int it = 0; it < kItems; ++it) {
-    const uint32_t d = (key[it] >> shift) & (kR - 1);
+    const uint32_t d = (key[it] >> shift) & (kRadix - 1);
     uint64_t peers = ~0ull;
 #pragma unroll
-    for (int b = 0; b < RB; ++b) {
+    for (int b = 0; b < kRadixBits; ++b) {
       const uint64_t bal = __ballot((d >> b) & 1u);
       peers &= ((d >> b) & 1u) ? bal : ~bal;
     }
@@ -331,30 +295,22 @@ radix_downsweep(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ v
   }
   __syncthreads();
   {  // per-digit prefix over waves, then tile-local digit starts
-    uint32_t v[DPT];
+    uint32_t s = 0;
+    if (tid < kRadix) {  // (threads past kRadix own no digit: they add 0 to the scan)
 #pragma unroll
-    for (int j = 0; j < DPT; ++j) {
-      const int d = tid * DPT + j;
-      uint32_t s = 0;
-      if (d < kR) {  // (threads past kR own no digit: they add 0 to the scan)
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-          const uint32_t c = wcnt[w][d];
-          wcnt[w][d] = s;
-          s += c;
-        }
+      for (int w = 0; w < kWaves; ++w) {
+        const uint32_t c = wcnt[w][tid];
+        wcnt[w][tid] = s;
+        s += c;
       }
-      v[j] = s;
     }
-    digits_exclusive_scan<DPT>(v, wsum, nullptr);
-#pragma unroll
-    for (int j = 0; j < DPT; ++j)
-      if (tid * DPT + j < kR) tstart[tid * DPT + j] = v[j];
+    const uint32_t ts = block_exclusive_scan(s, wsum, nullptr);
+    if (tid < kRadix) tstart[tid] = ts;
   }
   __syncthreads();
 #pragma unroll
   for (int it = 0; it < kItems; ++it) {
-    const uint32_t d = (key[it] >> shift) & (kR - 1);
+    const uint32_t d = (key[it] >> shift) & (kRadix - 1);
     const uint32_t pos = tstart[d] + wcnt[wv][d] + rank[it];
     skey[pos] = key[it];
     sval[pos] = val[it];
@@ -363,7 +319,7 @@ radix_downsweep(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ v
   const int64_t nvalid = n - base < kTile ? n - base : kTile;
   if constexpr (LINK) {
     if (local_ends && bounds && tid < nd) {  // digits without an element in this tile
-      const uint32_t e = tid + 1 < kR ? tstart[tid + 1] : (uint32_t)kTile;
+      const uint32_t e = tid + 1 < kRadix ? tstart[tid + 1] : (uint32_t)kTile;
       if (tstart[tid] == e) bnd[tile * nd + tid].kf = kRunEmpty;
     }
   }
@@ -372,35 +328,35 @@ radix_downsweep(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ v
     const int i = k * kThreads + tid;
     if (i < nvalid) {
       const uint32_t kk = skey[i];
-      const uint32_t d = (kk >> shift) & (kR - 1);
+      const uint32_t d = (kk >> shift) & (kRadix - 1);
       const int64_t o = local_ends ? 0 : (int64_t)gstart[d] + (i - (int64_t)tstart[d]);
       if constexpr (!LINK) {
-        st32<NT>(kout + o, kk);
-        st32<NT>(vout + o, sval[i]);
+        kout[o] = kk;
+        vout[o] = sval[i];
       } else {
-        const int hi = d + 1 < (uint32_t)kR ? (int)tstart[d + 1] : kTile;
+        const int hi = d + 1 < (uint32_t)kRadix ? (int)tstart[d + 1] : kTile;
         const bool first = i == (int)tstart[d];
         const bool last = i + 1 == hi || i + 1 >= nvalid;
         const uint32_t v = sval[i];
         if (bounds && (first || last)) {  // the fix-up reads the boundary pairs of every run
           if (local_ends) {
-            if ((int)d < nd) {  // (pads sort to digit kR - 1, past the schedule's digits)
+            if ((int)d < nd) {  // (pads sort to digit kRadix - 1, past the schedule's digits)
               RunEnds* r = bnd + tile * nd + d;
               if (first) { r->kf = kk; r->vf = v; }
               if (last) { r->kl = kk; r->vl = v; }
             }
           } else {
-            st32<NT>(kout + o, kk);
-            st32<NT>(vout + o, v);
+            kout[o] = kk;
+            vout[o] = v;
           }
         }
         if (kk < kend && v >= vlo && v < vhi) {  // this part's slot range (link_parts)
           uint32_t w = (!last && skey[i + 1] == kk) ? sval[i + 1] / (uint32_t)slots_per_match
                                                      : kNoMatch;
           if (!first && skey[i - 1] == kk) w |= kLinkHasPred;
-          // (non-temporal link stores alone measured 3.6 vs 1.6 ms per prepass: L2 write
-          // combining of these random 4-B stores matters, profiles/r3/ab_link_nt.log)
-          st32<NT>(link + v, w);
+          // (plain: non-temporal link stores alone measured 3.6 against 1.6 ms per prepass, L2
+          // write combining of these random 4-B stores matters, profiles/r3/ab_link_nt.log)
+          link[v] = w;
         }
       }
     }
@@ -417,13 +373,6 @@ radix_downsweep(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ v
 // parts 2 x 0.91 ms, its step 13.40 -> 12.56 ms.  Splitting config 2's 240 MB
 // as well costs more than it saves (8.13 -> 8.46 ms).  ANA_LINK_PARTS overrides
 // the count (1 = one pass).
-// ANA_SCHED_RUNS=0: the last pass with digit offsets + sched_fixup (the round-2 path),
-// for A/B; default: the run table (radix_downsweep bnd, sched_runs_fixup)
-static bool local_runs() {  // per schedule: tests switch it at run time
-  const char* e = getenv("ANA_SCHED_RUNS");
-  return !(e && atoi(e) == 0);
-}
-
 static int link_parts(int64_t n) {
   if (const char* e = getenv("ANA_LINK_PARTS")) {  // per launch: tests switch it at run time
     const int v = atoi(e);
@@ -437,19 +386,17 @@ static int link_parts(int64_t n) {
 // (tile, digit) run; its first pair's predecessor and its last pair's successor
 // are the last / first pairs of the neighbouring runs, which that pass wrote.
 // Grid: (tile groups of 256, digits); blocks of empty digits exit at once.
-template <int RB = 8>
 __global__ void __launch_bounds__(kThreads)
 sched_fixup(const uint32_t* __restrict__ kout, const uint32_t* __restrict__ vout, int64_t n,
             uint32_t kend, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ totals,
             int64_t tiles, int slots_per_match, uint32_t* __restrict__ link) {
-  constexpr int kR = 1 << RB;
   __shared__ uint32_t wsum[kWaves];
   const int d = blockIdx.y;
   const uint32_t tot = totals[d];
   if (tot == 0) return;
   uint32_t below = 0;
 #pragma unroll
-  for (int j = threadIdx.x; j < kR; j += kThreads) below += j < d ? totals[j] : 0u;
+  for (int j = threadIdx.x; j < kRadix; j += kThreads) below += j < d ? totals[j] : 0u;
   uint32_t all = 0;
   const uint32_t before = block_exclusive_scan(below, wsum, &all);
   (void)before;
@@ -598,7 +545,6 @@ __device__ __forceinline__ void chain_sort_round(const uint32_t (&key)[kItems], 
   }
   __syncthreads();
   {  // per-digit prefix over waves, then tile-local digit starts
-    uint32_t v[1];
     uint32_t s = 0;
     if (tid < kR) {
 #pragma unroll
@@ -608,9 +554,8 @@ __device__ __forceinline__ void chain_sort_round(const uint32_t (&key)[kItems], 
         s += c;
       }
     }
-    v[0] = s;
-    digits_exclusive_scan<1>(v, wsum, nullptr);
-    if (tid < kR) tstart[tid] = v[0];
+    const uint32_t ts = block_exclusive_scan(s, wsum, nullptr);
+    if (tid < kR) tstart[tid] = ts;
   }
   __syncthreads();
 #pragma unroll
@@ -640,7 +585,7 @@ constexpr uint32_t kLinkSkip = 0xffffffffu;      // no link for this slot: sched
 // (LINES: 116 KB of LDS, else 84 KB: one workgroup per CU, two waves per SIMD.  The link
 // loops are unrolled by 2 only: fully unrolled the compiler takes 236 VGPRs, and two such waves
 // no longer fit on a SIMD beside a wave of the executor)
-template <int KS, int NT, bool LINES>
+template <int KS, bool NT, bool LINES>
 __global__ void __launch_bounds__(kThreads)
 sched_chain(uint32_t* kio, const uint32_t* __restrict__ vin,
             const int32_t* __restrict__ rec, uint32_t kend, int64_t n, int low,
@@ -772,12 +717,14 @@ sched_chain(uint32_t* kio, const uint32_t* __restrict__ vin,
         }
       }
       __syncthreads();  // lbuf holds every link of the previous tile that this tile resolves
+      // (the address as kio + start, then + prev + j: written kio[start + prev + j] the compiler
+      // schedules this kernel differently, 0.01-0.02 ms per prepass, profiles/r10/sched_variants_ab.log)
       if (base > 0) {   // (a previous tile is a full tile)
 #pragma unroll 2
         for (int k = 0; k < kItems; ++k) {
           const int j = k * kThreads + tid;
           const uint32_t w = lbuf[j];
-          if (w != kLinkDeferred) st32<NT>(kio + start + prev + j, w);
+          if (w != kLinkDeferred) *(kio + start + prev + j) = w;
         }
       }
 #pragma unroll 2
@@ -827,7 +774,7 @@ sched_chain(uint32_t* kio, const uint32_t* __restrict__ vin,
       }
     }
     __syncthreads();
-    for (int64_t j = tid; j < cnt - lastb; j += kThreads) st32<NT>(kio + start + lastb + j, lbuf[j]);
+    for (int64_t j = tid; j < cnt - lastb; j += kThreads) *(kio + start + lastb + j) = lbuf[j];
   }
 }
 
@@ -838,16 +785,14 @@ sched_chain(uint32_t* kio, const uint32_t* __restrict__ vin,
 // what sched_chain left in place of the keys), places each link in LDS at slot - tile start
 // and writes link[tile] as whole lines.  Slots that get no link -- the buckets nobody chains
 // (d >= nb) and kLinkSkip -- are left alone.
-template <int RB, int NT>
+template <bool NT>
 __global__ void __launch_bounds__(kThreads)
 sched_unpartition(const uint32_t* __restrict__ lk, const uint32_t* __restrict__ vo, int64_t n,
                   const uint32_t* __restrict__ counts, const uint32_t* __restrict__ totals,
                   int64_t tiles, int nb, uint32_t* __restrict__ link) {
-  constexpr int kR = 1 << RB;
-  static_assert(kR <= kThreads, "one digit per thread");
   __shared__ uint32_t out[kTile];
-  __shared__ uint32_t tstart[kR];  // start of each digit's run in the (sorted) tile
-  __shared__ uint32_t gstart[kR];  // ... and in the partitioned arrays
+  __shared__ uint32_t tstart[kRadix];  // start of each digit's run in the (sorted) tile
+  __shared__ uint32_t gstart[kRadix];  // ... and in the partitioned arrays
   __shared__ uint32_t wsum[kWaves];
   const int tid = threadIdx.x;
   const int64_t tile = xcd_tile(tiles);
@@ -859,9 +804,9 @@ sched_unpartition(const uint32_t* __restrict__ lk, const uint32_t* __restrict__ 
     len = (tile + 1 < tiles ? counts[(int64_t)tid * tiles + tile + 1] : totals[tid]) - c0;
   }
   uint32_t nchain = 0u;
-  const uint32_t g = block_exclusive_scan(tid < kR ? totals[tid] : 0u, wsum, nullptr);
+  const uint32_t g = block_exclusive_scan(tid < kRadix ? totals[tid] : 0u, wsum, nullptr);
   const uint32_t ts = block_exclusive_scan(len, wsum, &nchain);
-  if (tid < kR) {
+  if (tid < kRadix) {
     gstart[tid] = g + c0;
     tstart[tid] = ts;  // (digits >= nb: nchain, past every element)
   }
@@ -874,7 +819,7 @@ sched_unpartition(const uint32_t* __restrict__ lk, const uint32_t* __restrict__ 
     if (i < nchain) {
       uint32_t d = 0u;  // the last digit whose run starts at or before i (the runs before it may be empty)
 #pragma unroll
-      for (uint32_t step = kR >> 1; step > 0u; step >>= 1)
+      for (uint32_t step = kRadix >> 1; step > 0u; step >>= 1)
         if (tstart[d + step] <= i) d += step;
       const int64_t o = (int64_t)gstart[d] + (i - tstart[d]);
       if (o < n) {
@@ -904,7 +849,7 @@ sched_unpartition(const uint32_t* __restrict__ lk, const uint32_t* __restrict__ 
 
 size_t radix_sort_workspace_bytes(int64_t n) {
   const int64_t tiles = (n + kTile - 1) / kTile;
-  return (size_t)(tiles * kRadixMax + kRadixMax) * 4;
+  return (size_t)(tiles * kRadix + kRadix) * 4;  // counts[kRadix][tiles], totals[kRadix]
 }
 
 int launch_radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt,
@@ -931,16 +876,15 @@ int launch_radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, 
 
 // The schedule's sort (K5): the slots of the stream by player, stable, fused at
 // both ends -- the first pass reads the records (no key array is written), the
-// last pass writes links instead of sorted pairs, then sched_fixup.  RB-bit
-// digits (8; 10 as an experiment).
-template <int K, int RB, int NT>
+// last pass writes links instead of sorted pairs, then a fix-up of the run boundaries.
+// NT: the passes stream their input with non-temporal loads (ld32).
+template <int K, bool NT>
 static void sched_sort_k(const int32_t* rec, int64_t n, uint32_t kend, int bits, uint32_t* ka,
                          uint32_t* va, uint32_t* kb, uint32_t* vb, uint32_t* counts,
                          int64_t tiles, uint32_t* link, const SchedInit& init, bool chain,
                          hipStream_t s) {
   constexpr int S = 2 * K;
-  constexpr int kR = 1 << RB;
-  uint32_t* totals = counts + tiles * kR;
+  uint32_t* totals = counts + tiles * kRadix;
   const dim3 grid((unsigned)tiles), block(kThreads);
   const uint32_t *ki = nullptr, *vi = nullptr;
   uint32_t *ko = kb, *vo = vb;
@@ -952,23 +896,23 @@ static void sched_sort_k(const int32_t* rec, int64_t n, uint32_t kend, int bits,
       // make its workgroup the long pole, so the partition keys them with the first key of
       // bucket nb instead, which no workgroup chains (when nb is a digit of its own, < 256).
       const uint32_t nb = ((kend - 1u) >> low) + 1u;
-      const uint32_t knone = nb < (uint32_t)kR ? nb << low : kend;
-      hipLaunchKernelGGL((radix_upsweep<K, RB, NT>), grid, block, 0, s, nullptr, rec, kend, n, low, counts, tiles,
+      const uint32_t knone = nb < (uint32_t)kRadix ? nb << low : kend;
+      hipLaunchKernelGGL((radix_upsweep<K, NT>), grid, block, 0, s, nullptr, rec, kend, n, low, counts, tiles,
                          init, knone);
-      hipLaunchKernelGGL(radix_rowscan, dim3(kR), block, 0, s, counts, tiles, totals);
-      hipLaunchKernelGGL((radix_downsweep<K, false, RB, NT>), grid, block, 0, s, nullptr, nullptr, rec, kend, ko,
+      hipLaunchKernelGGL(radix_rowscan, dim3(kRadix), block, 0, s, counts, tiles, totals);
+      hipLaunchKernelGGL((radix_downsweep<K, false, NT>), grid, block, 0, s, nullptr, nullptr, rec, kend, ko,
                          vo, n, low, counts, totals, tiles, S, nullptr, 0u, 0xffffffffu, 1, nullptr, 0, knone);
       // A prepass beside the executor (its caller streams the sort's input with non-temporal
-      // loads: sort_nt / ANA_SORT_NT >= 1) writes the links as whole lines: the executor pays
+      // loads: sort_nt / ANA_SORT_NT = 2) writes the links as whole lines: the executor pays
       // for the prepass's write requests, and the step is 0.27-0.37 ms shorter.  A prepass with
       // nothing beside it keeps the direct stores: alone they are 0.32 ms faster per window
       // (config 2 with ANA_PREPASS_SERIAL=1: 6.32-6.37 against 6.69-6.72 ms with whole lines).
-      if constexpr (NT != 0 && kR <= kThreads) {  // (the 10-bit experiment never takes the chain path)
+      if constexpr (NT) {
         // once, whatever ANA_LINK_PARTS says: there is no randomly written link array to keep
         // inside the Infinity Cache
         hipLaunchKernelGGL((sched_chain<0, NT, true>), dim3(nb), block, 0, s, ko, vo, nullptr, kend, n, low,
                            totals, S, nullptr, 0u, 0xffffffffu, n / S, SchedInit{});
-        hipLaunchKernelGGL((sched_unpartition<RB, NT>), grid, block, 0, s, ko, vo, n, counts, totals, tiles,
+        hipLaunchKernelGGL(sched_unpartition<NT>, grid, block, 0, s, ko, vo, n, counts, totals, tiles,
                            (int)nb, link);
       } else {
         const int parts = link_parts(n);
@@ -986,18 +930,23 @@ static void sched_sort_k(const int32_t* rec, int64_t n, uint32_t kend, int bits,
     }
     return;
   }
-  for (int shift = 0; shift < bits; shift += RB) {
-    const bool first = shift == 0, last = shift + RB >= bits;
+  for (int shift = 0; shift < bits; shift += kRadixBits) {
+    const bool first = shift == 0, last = shift + kRadixBits >= bits;
     // the last pass of a multi-pass sort over few digits (1M players: bits 16..19, 16
-    // digits): run ends in a table, no digit offsets (radix_downsweep bnd)
-    const int nd = bits - shift < RB ? 1 << (bits - shift) : kR;
-    if (last && !first && nd <= kRunsMaxDigits && local_runs()) {
-      RunEnds* bnd = reinterpret_cast<RunEnds*>(counts);  // pass counts are consumed by now
+    // digits): run ends in a table, no digit offsets (radix_downsweep bnd).  A last pass over
+    // more digits (config 5, 10M players: 256) takes the digit offsets and sched_fixup below.
+    const int nd = bits - shift < kRadixBits ? 1 << (bits - shift) : kRadix;
+    if (last && !first && nd <= kRunsMaxDigits) {
+      // The table lives in the counts region, whose pass counts are consumed by now: that
+      // region is kRadix * 4 = 1024 B per tile (+ 1024 B of totals); bnd takes nd * 16 <= 512 B
+      // per tile (nd <= kRunsMaxDigits = 32) and seglast nd * 4 <= 128 B per segment of
+      // kThreads tiles, i.e. under 1 B per tile + 128 B.
+      RunEnds* bnd = reinterpret_cast<RunEnds*>(counts);
       const int64_t nseg = (tiles + kThreads - 1) / kThreads;
       int32_t* seglast = reinterpret_cast<int32_t*>(bnd + tiles * nd);
       const int parts = link_parts(n);
       for (int q = 0; q < parts; ++q)
-        hipLaunchKernelGGL((radix_downsweep<0, true, RB, NT>), grid, block, 0, s, ki, vi, nullptr, kend, ko, vo,
+        hipLaunchKernelGGL((radix_downsweep<0, true, NT>), grid, block, 0, s, ki, vi, nullptr, kend, ko, vo,
                            n, shift, counts, totals, tiles, S, link, (uint32_t)(n * q / parts),
                            (uint32_t)(n * (q + 1) / parts), q == 0 ? 1 : 0, bnd, nd);
       const dim3 sgrid((unsigned)nseg, (unsigned)nd);
@@ -1006,30 +955,30 @@ static void sched_sort_k(const int32_t* rec, int64_t n, uint32_t kend, int bits,
       break;
     }
     if (first)
-      hipLaunchKernelGGL((radix_upsweep<K, RB, NT>), grid, block, 0, s, nullptr, rec, kend, n, shift, counts, tiles,
+      hipLaunchKernelGGL((radix_upsweep<K, NT>), grid, block, 0, s, nullptr, rec, kend, n, shift, counts, tiles,
                          init);
     else
-      hipLaunchKernelGGL((radix_upsweep<0, RB, NT>), grid, block, 0, s, ki, nullptr, kend, n, shift, counts, tiles);
-    hipLaunchKernelGGL(radix_rowscan, dim3(kR), block, 0, s, counts, tiles, totals);
+      hipLaunchKernelGGL((radix_upsweep<0, NT>), grid, block, 0, s, ki, nullptr, kend, n, shift, counts, tiles);
+    hipLaunchKernelGGL(radix_rowscan, dim3(kRadix), block, 0, s, counts, tiles, totals);
     const int parts = last ? link_parts(n) : 1;
     if (first && last)
       for (int q = 0; q < parts; ++q)
-        hipLaunchKernelGGL((radix_downsweep<K, true, RB, NT>), grid, block, 0, s, nullptr, nullptr, rec, kend, ko,
+        hipLaunchKernelGGL((radix_downsweep<K, true, NT>), grid, block, 0, s, nullptr, nullptr, rec, kend, ko,
                            vo, n, shift, counts, totals, tiles, S, link, (uint32_t)(n * q / parts),
                            (uint32_t)(n * (q + 1) / parts), q == 0 ? 1 : 0);
     else if (first)
-      hipLaunchKernelGGL((radix_downsweep<K, false, RB, NT>), grid, block, 0, s, nullptr, nullptr, rec, kend, ko,
+      hipLaunchKernelGGL((radix_downsweep<K, false, NT>), grid, block, 0, s, nullptr, nullptr, rec, kend, ko,
                          vo, n, shift, counts, totals, tiles, S, nullptr);
     else if (last)
       for (int q = 0; q < parts; ++q)
-        hipLaunchKernelGGL((radix_downsweep<0, true, RB, NT>), grid, block, 0, s, ki, vi, nullptr, kend, ko, vo,
+        hipLaunchKernelGGL((radix_downsweep<0, true, NT>), grid, block, 0, s, ki, vi, nullptr, kend, ko, vo,
                            n, shift, counts, totals, tiles, S, link, (uint32_t)(n * q / parts),
                            (uint32_t)(n * (q + 1) / parts), q == 0 ? 1 : 0);
     else
-      hipLaunchKernelGGL((radix_downsweep<0, false, RB, NT>), grid, block, 0, s, ki, vi, nullptr, kend, ko, vo, n,
+      hipLaunchKernelGGL((radix_downsweep<0, false, NT>), grid, block, 0, s, ki, vi, nullptr, kend, ko, vo, n,
                          shift, counts, totals, tiles, S, nullptr);
     if (last)
-      hipLaunchKernelGGL((sched_fixup<RB>), dim3((unsigned)((tiles + kThreads - 1) / kThreads), kR), block,
+      hipLaunchKernelGGL(sched_fixup, dim3((unsigned)((tiles + kThreads - 1) / kThreads), kRadix), block,
                          0, s, ko, vo, n, kend, counts, totals, tiles, S, link);
     ki = ko;
     vi = vo;
@@ -1054,20 +1003,15 @@ int launch_sched_sort(int K, const int32_t* rec, int64_t M, uint32_t num_players
   init.ctrl = ctrl;
   init.nz = ctrl ? nz : 0;
   init.epoch_bump = epoch_bump;
-  // ANA_SORT_RB=10: 10-bit digits (2 passes for <= 2^20 players instead of 3).  Measured
-  // on MI355X, 10M 3v3 / 1M players: 3.11 ms vs 1.76 ms for 8-bit digits (1024
-  // per-tile runs of ~4 elements scatter the pass's writes) -> off by default.
-  // read per schedule, like ANA_SCHED_RUNS / ANA_LINK_PARTS: A/B runs and tests switch
-  // them inside one process
-  const char* rb_e = getenv("ANA_SORT_RB");
+  // Non-temporal loads: 0 (none) or 2 (every pass streams its input).  sort_nt >= 0 is the
+  // caller's choice (WindowPipeline: 2 for a prepass beside the executor); ANA_SORT_NT wins,
+  // read per schedule like ANA_SCHED_CHAIN / ANA_LINK_PARTS, so that tests reach the
+  // whole-lines path through BatchRater.rate.  Any other value is refused before a launch.
   const char* nt_e = getenv("ANA_SORT_NT");
-  const int rb_env = rb_e ? atoi(rb_e) : 8;
-  // sort_nt >= 0: the caller's choice (WindowPipeline: loads-only between DP merges)
   const int nt = nt_e ? atoi(nt_e) : sort_nt >= 0 ? sort_nt : 0;
-  const bool wide = bits <= 20 && rb_env == 10;
+  if (nt != 0 && nt != 2) return (int)hipErrorInvalidValue;
   // The chain pass (sched_chain) for rosters of <= 2^20 players; above that (config 5) the
-  // three LSD passes stay.  ANA_SCHED_CHAIN=1 / 0 forces it / the LSD passes; the
-  // ANA_SORT_RB=10 and ANA_SCHED_RUNS=0 experiments select the LSD passes they belong to.
+  // three LSD passes stay.  ANA_SCHED_CHAIN=1 / 0 forces it / the LSD passes.
   // Unforced, the chain pass runs where its one workgroup per bucket is not the long pole.
   // A workgroup chains a tile in ~26 us (0.79 ms for the 30 tiles of a config 2 bucket),
   // the LSD passes take ~27 ps per slot (1.6 ms for 60M) on top of ~40 us of launches:
@@ -1077,14 +1021,11 @@ int launch_sched_sort(int K, const int32_t* rec, int64_t M, uint32_t num_players
   const char* chain_e = getenv("ANA_SCHED_CHAIN");
   const int top = bits > kChainLowBits ? bits - kChainLowBits : 0;
   const bool chain_pays = (n >> top) <= 2 * kTile + n / 128;
-  const bool chain = (chain_e ? atoi(chain_e) != 0 : kChainDefault && chain_pays) && bits <= 20 && !wide &&
-                     local_runs();
+  const bool chain = (chain_e ? atoi(chain_e) != 0 : kChainDefault && chain_pays) && bits <= 20;
   const bool known = with_team_size(K, [&](auto k) {
     constexpr int kK = decltype(k)::value;
-    if (wide) sched_sort_k<kK, 10, 0>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, chain, s);
-    else if (nt == 1) sched_sort_k<kK, 8, 1>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, chain, s);
-    else if (nt == 2) sched_sort_k<kK, 8, 2>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, chain, s);
-    else sched_sort_k<kK, 8, 0>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, chain, s);
+    if (nt == 2) sched_sort_k<kK, true>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, chain, s);
+    else sched_sort_k<kK, false>(rec, n, num_players, bits, ka, va, kb, vb, counts, tiles, link, init, chain, s);
   });
   return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }

@@ -305,9 +305,9 @@ class BatchRater:
         follows it on the same stream -- never from a side stream, where a rate
         launch may be using them.  ``epoch_bump``: a device int32 launch epoch
         (graph replays) the schedule increments, saving the bump its own dispatch.
-        ``sort_nt``: non-temporal accesses of the radix sort (0 none, 1 all, 2 loads
-        only; -1: ANA_SORT_NT or none) -- ANA_SORT_NT, when set, wins.  It is what a prepass
-        beside the executor asks for, so with 1 or 2 the chain path (rosters up to 2^20 players)
+        ``sort_nt``: non-temporal loads of the radix sort (0 none, 2 loads; -1: ANA_SORT_NT
+        or none; anything else is refused) -- ANA_SORT_NT, when set, wins.  2 is what a prepass
+        beside the executor asks for, so with it the chain path (rosters up to 2^20 players)
         also writes its links as whole lines: fewer write requests next to the executor, a
         longer prepass on its own (csrc/radix_sort.hip)."""
         M = rec.shape[0]

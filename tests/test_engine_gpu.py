@@ -53,11 +53,13 @@ def test_generators_bit_identical(gpu_device):
 
 # 1 (P=20), 2 (P=300, 5000), 3 (P=70k) and 4 (P=17M) radix passes: every
 # combination of the fused first / last passes of the schedule sort
-# + micro-batches (<= 8192 slots): the one-workgroup LDS bitonic schedule
+# + micro-batches (<= 8192 slots): the one-workgroup LDS hash-list schedule
 # + every team size on both paths: K = 4 in one workgroup, K = 1, 2, 4 at the smallest
 #   windows of the sort path (> 8192 slots)
+# + P=40k: a last pass over 256 digits behind another pass (digit offsets and sched_fixup,
+#   the last pass of a 10M-player roster; up to 32 digits it is the run table)
 @pytest.mark.parametrize("P,M,K", [(20, 3000, 3), (5000, 100000, 3), (300, 20000, 5),
-                                   (70_000, 400_000, 3), (17_000_000, 300_000, 3),
+                                   (70_000, 400_000, 3), (17_000_000, 300_000, 3), (40_000, 100_000, 3),
                                    (50, 400, 3), (5000, 819, 5), (1_000_000, 1365, 3), (20, 1, 1),
                                    (40, 700, 2), (40, 700, 4), (40, 5000, 1), (40, 3000, 2),
                                    (40, 1100, 4)])
@@ -77,21 +79,23 @@ def test_schedule_matches_host(gpu_device, P, M, K):
     np.testing.assert_array_equal(need[rated], deps_h.numpy()[rated])
 
 
-@pytest.mark.parametrize("P,M,K,skew,runs,rb", [(1_000_000, 400_000, 3, 3, "1", "8"),
-                                                (1_000_000, 400_000, 3, 1, "0", "8"),
-                                                (1_000_000, 400_000, 3, 1, "1", "8"),
-                                                (5000, 300_000, 5, 2, "1", "8"),
-                                                (5000, 300_000, 3, 2, "1", "10"),
-                                                (300_000, 400_000, 3, 1, "1", "10")])
-def test_schedule_run_table_matches_host(gpu_device, P, M, K, skew, runs, rb, monkeypatch):
+@pytest.mark.parametrize("P,M,K,skew", [(1_000_000, 400_000, 3, 3),
+                                        (1_000_000, 400_000, 3, 1),
+                                        (5000, 300_000, 5, 2),
+                                        (5000, 300_000, 3, 2),
+                                        (300_000, 400_000, 3, 1)])
+def test_schedule_run_table_matches_host(gpu_device, P, M, K, skew, monkeypatch):
     """The last sort pass with run ends in a [tile][digit] table (no digit offsets,
-    sched_runs_fixup) and the round-2 path (ANA_SCHED_RUNS=0): the same links as the
-    host, also on power-law streams where a hot player's runs span many tiles and a
-    sparse player's nearest earlier run lies tiles back.  ANA_SORT_RB=10 (10-bit
-    digits, read per schedule): a small roster's single pass (<= 1024 digits) and a
-    two-pass one, both through the run table."""
-    monkeypatch.setenv("ANA_SCHED_RUNS", runs)
-    monkeypatch.setenv("ANA_SORT_RB", rb)
+    sched_runs_fixup): the same links as the host, also on power-law streams where a
+    hot player's runs span many tiles and a sparse player's nearest earlier run lies
+    tiles back.  ANA_SCHED_CHAIN=0 keeps every case on the LSD passes (unforced, the
+    windows over 1M and 300k players take the chain pass), so each reaches the table:
+    last passes of 16, 16, 32, 32 and 8 digits, the third pass of three or the second
+    of two.  The other last pass -- digit offsets and sched_fixup -- is covered by
+    test_schedule_matches_host and test_schedule_link_parts_match_host: fused with the
+    first pass at P = 20 in both, and as the 256-digit second pass of P = 40k in the
+    former (the 17M-player cases end in a fourth pass over 2 digits: the table again)."""
+    monkeypatch.setenv("ANA_SCHED_CHAIN", "0")
     rec = make_stream(StreamSpec(team_size=K, seed=P + skew, skew=skew, p_afk=0.05), M, P, K=K)
     br = R.BatchRater()
     link_h, deps_h = (t.clone() for t in br.schedule(rec, K, P))
@@ -117,6 +121,26 @@ def test_schedule_link_parts_match_host(gpu_device, P, M, K, monkeypatch):
     need = (first & ((link_d & R.Schedule.HAS_PRED) != 0)).sum(1)
     rated = slots.any(1)
     np.testing.assert_array_equal(need[rated], deps_h.numpy()[rated])
+
+
+def test_schedule_refuses_unknown_sort_nt(gpu_device, monkeypatch):
+    """ANA_SORT_NT=1 (once: non-temporal stores as well) is refused, not mapped onto a
+    surviving kernel: the smallest window of the sort path (8196 slots, one more than a
+    micro-batch) raises before anything is launched, and the same call without the
+    variable then gives the host's links -- the refusal left nothing behind."""
+    P, M, K = 5000, 1366, 3
+    rec = make_stream(StreamSpec(team_size=K, seed=7, p_afk=0.05, p_hot=0.2), M, P, K=K)
+    br = R.BatchRater()
+    link_h, deps_h = (t.clone() for t in br.schedule(rec, K, P))
+    rec_d = rec.to(gpu_device)
+    monkeypatch.setenv("ANA_SORT_NT", "1")
+    with pytest.raises(RuntimeError):
+        br.schedule(rec_d, K, P)
+    monkeypatch.delenv("ANA_SORT_NT")
+    link_d, deps_d = br.schedule(rec_d, K, P)
+    slots, _ = _stateful_slots(rec.numpy(), K, P)
+    np.testing.assert_array_equal(link_d.cpu().numpy()[slots], link_h.numpy()[slots])
+    assert int(deps_d.abs().sum()) == 0
 
 
 @pytest.mark.parametrize("name", sorted(SPECS))

@@ -261,3 +261,22 @@ def test_bindings_reject_team_size_out_of_range(name, K):
             call(native(), ok)
         except RuntimeError as e:  # (records_digest: "device rows" on the CPU)
             assert "1..5" not in str(e), e
+
+
+def test_schedule_rejects_unknown_sort_nt():
+    """sort_nt is 0 (plain loads), 2 (non-temporal loads) or -1 (ANA_SORT_NT or plain): any
+    other value is refused on the CPU path too, where it would otherwise go unread -- 1 used
+    to select a variant with non-temporal stores and is not mapped onto a surviving one."""
+    from analyzer_amd.ops.native import native
+
+    M, K, P = 2, 3, 4
+    rec = make_stream(StreamSpec(team_size=K, seed=1), M, P, K=K)
+    args = lambda: (rec, K, P, torch.zeros(M, 2 * K, dtype=torch.int32), torch.zeros(M, dtype=torch.int32),  # noqa: E731
+                    torch.empty(0, dtype=torch.uint8), torch.zeros(0, dtype=torch.int32), False, 0)
+    for bad in (1, 3, -2):
+        with pytest.raises(RuntimeError, match="sort_nt"):
+            native().schedule(*args(), bad)
+    for ok in (-1, 0, 2):
+        native().schedule(*args(), ok)
+    with pytest.raises(RuntimeError, match="sort_nt"):
+        R.BatchRater().schedule(rec, K, P, sort_nt=1)

@@ -68,12 +68,11 @@ def long_bucket():
     return stream(5000, 20000, 3, p_hot=0.2, p_uneven=0.05)
 
 
-@pytest.mark.parametrize("nt", ["2", "1"])
+@pytest.mark.parametrize("nt", ["2"])
 def test_lag_buffer_and_older_tiles(gpu_device, monkeypatch, nt):
     """A bucket of 12 tiles: links resolved in the next tile (the LDS buffer), links deferred
     past it (the plain store at the bucket position, masked out of the flush), and the
-    final flush.  The input has all three, by the host's own layout.  (nt = 1: the variant
-    with non-temporal stores as well.)"""
+    final flush.  The input has all three, by the host's own layout."""
     monkeypatch.setenv("ANA_SORT_NT", nt)
     P, K = 5000, 3
     rec = long_bucket()
