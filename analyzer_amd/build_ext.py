@@ -29,7 +29,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 HIP_SOURCES = ["kernels.hip", "radix_sort.hip", "dataflow.hip", "sweep.hip", "telemetry.hip", "levels.hip",
                "digest.hip", "select.hip", "ladder.hip", "matchmake.hip", "career.hip", "score.hip",
-               "pairs.hip", "scan.hip"]
+               "pairs.hip", "scan.hip", "profile.hip"]
 # per-file device flags.  The executor's divisions/sqrt take the 1-ulp hardware
 # paths (v_rcp_f32 instead of the ~10-instruction IEEE division expansion: -9%
 # static instructions); NaN/Inf semantics are untouched (no -ffinite-math-only),
@@ -43,6 +43,8 @@ HIP_FLAGS["matchmake.hip"] = ["-ffp-contract=off"]
 HIP_FLAGS["career.hip"] = ["-ffp-contract=off"]
 # the scorecard's d and sum sigma^2 are the sums the preview kernel forms (csrc/score.hip)
 HIP_FLAGS["score.hip"] = ["-ffp-contract=off"]
+# a profile's bracket comes from the same score (csrc/profile_core.h)
+HIP_FLAGS["profile.hip"] = ["-ffp-contract=off"]
 CPP_SOURCES = ["host.cpp", "ingest.cpp", "batch_host.cpp", "telemetry_file.cpp", "bindings.cpp"]
 
 

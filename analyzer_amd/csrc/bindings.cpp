@@ -23,6 +23,7 @@
 #include "ladder_core.h"
 #include "matchmake_core.h"
 #include "pair_core.h"
+#include "profile_core.h"
 #include "score_core.h"
 #include "select_core.h"
 
@@ -975,6 +976,64 @@ void careers_add(Tensor table, Tensor rec, Tensor rows, int64_t base, int64_t P,
             "career_fold");
 }
 
+// K17 (profile.hip; host mirror host.cpp host_profiles_add): folds the games of one window -- rec
+// [M, 2K+2] joined with its packed output rows [M, W] and its stat vectors stats [M, 2K, 8] --
+// into the player table [P, 20] int32 and the baseline table cells [6 * B * 2 * 9 + 2] int64 in
+// place (profile_core.h); edges: the B - 1 bracket edges, fp32 on the CPU.  Dispatches on the
+// tensors' device; the device path is four stream-ordered steps (keys, sort, fold, stitch).
+void profiles_add(Tensor table, Tensor cells, Tensor rec, Tensor rows, Tensor stats, int64_t P, int64_t track,
+                  int64_t score, int64_t modes, Tensor edges) {
+  const auto dev = table.device();
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "profiles_add: rec must be [M, 2K+2]");
+  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t M = check_window(rec, rows, K, dev, "profiles_add");
+  check_slots(M, K, "profiles_add");
+  TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "profiles_add: P must fit in int32");
+  check_rows(table, "table", P, ana::kProfileWords, dev, torch::kInt32);
+  check(stats, "stats", torch::kFloat32, dev);
+  TORCH_CHECK(stats.dim() == 3 && stats.size(0) == M && stats.size(1) == 2 * K && stats.size(2) == ana::kProfileStats,
+              "profiles_add: stats must be [M, 2K, 8]");
+  check(edges, "edges", torch::kFloat32, torch::Device(torch::kCPU));
+  TORCH_CHECK(edges.dim() == 1 && edges.numel() <= ana::kProfileMaxEdges, "profiles_add: at most ",
+              ana::kProfileMaxEdges, " edges");
+  const int n_edges = (int)edges.numel();
+  const float* ep = edges.data_ptr<float>();
+  for (int i = 0; i < n_edges; ++i)
+    TORCH_CHECK(std::isfinite(ep[i]) && (i == 0 || ep[i - 1] < ep[i]),
+                "profiles_add: edges must be finite and strictly ascending");
+  check(cells, "cells", torch::kInt64, dev);
+  TORCH_CHECK(cells.numel() == ana::profile_table_words(n_edges + 1), "profiles_add: cells must hold ",
+              ana::profile_table_words(n_edges + 1), " words");
+  TORCH_CHECK(track == ana::kCareerShared || track == ana::kCareerMode, "profiles_add: unknown track ", track);
+  TORCH_CHECK(score == ana::kLadderConservative || score == ana::kLadderMu, "profiles_add: unknown score ", score);
+  TORCH_CHECK(modes >= 0 && (modes & ~(int64_t)ana::kCareerAllModes) == 0,
+              "profiles_add: the modes mask must name modes 0..5");
+  if (M == 0 || P == 0) return;
+  if (!dev.is_cuda()) {
+    TORCH_CHECK(ana::host_profiles_add((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1),
+                                       stats.data_ptr<float>(), M, P, (int)track, (int)score, (uint32_t)modes, ep,
+                                       n_edges, table.data_ptr<int32_t>(), cells.data_ptr<int64_t>()) == 0,
+                "profiles_add: bad arguments");
+    return;
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(stats.data_ptr()) % 16 == 0,
+              "profiles_add: table and stats must be 16-B aligned");
+  const hipStream_t s = stream_of(table);
+  const int64_t n = M * 2 * K;
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
+  Tensor keys = torch::empty({n}, i32), vals = torch::empty({n}, i32);
+  check_hip(ana::launch_profile_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1),
+                                     stats.data_ptr<float>(), M, P, (int)track, (int)score, (uint32_t)modes, ep,
+                                     n_edges, u32p(keys), u32p(vals), cells.data_ptr<int64_t>(), s),
+            "profile_keys");
+  const auto sorted = sort_pairs_on_stream(keys, vals, n, bit_length(P), s);
+  Tensor fold_edges = torch::empty({(int64_t)ana::profile_edge_bytes(n)}, i32.dtype(torch::kUInt8));
+  check_hip(ana::launch_profile_fold(u32p(sorted[0]), u32p(sorted[1]), stats.data_ptr<float>(), n, (int)K, P,
+                                     table.data_ptr<int32_t>(), fold_edges.data_ptr<uint8_t>(), s),
+            "profile_fold");
+}
+
 // priors [M, 4 * 2K] fp32 (field-major: shared mu, sigma, mode mu, sigma) of one window against
 // the chain table [P, 16] (mu, sigma per granule), which is advanced in place to the state
 // after the window (score_core.h).  The device path is six stream-ordered steps (keys, sort,
@@ -1477,6 +1536,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "career table [P, 16] int32 in place: careers_add(table, rec, rows, base, P, track, score, modes)");
   m.attr("CAREER_WORDS") = ana::kCareerWords;
   m.attr("CAREER_TILE") = ana::kCareerTile;
+  m.def("profiles_add", &profiles_add, "K17: fold one window (rec [M, 2K+2] joined with its packed rows [M, W] and "
+        "its stat vectors stats [M, 2K, 8]) into the player table [P, 20] int32 and the baseline table int64 in "
+        "place: profiles_add(table, cells, rec, rows, stats, P, track, score, modes, edges)");
+  m.attr("PROFILE_WORDS") = ana::kProfileWords;
+  m.attr("PROFILE_TILE") = ana::kProfileTile;
   m.def("priors_add", &priors_add, "K14: the pre-match priors [M, 4 * 2K] fp32 of one window (rec [M, 2K+2] joined with "
         "its packed rows [M, W]) against the chain table [P, 16], advanced in place: priors_add(chain, rec, rows)");
   m.def("score_add", &score_add, "K14: add the predictions of a window's priors to the scorecard table [6, 33, 4] int64 "

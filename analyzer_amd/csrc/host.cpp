@@ -17,6 +17,7 @@
 #include "ladder_core.h"
 #include "matchmake_core.h"
 #include "pair_core.h"
+#include "profile_core.h"
 #include "rate_core.h"
 #include "score_core.h"
 #include "select_core.h"
@@ -389,6 +390,48 @@ int host_careers_add(int K, const int32_t* rec, const float* rows, int64_t W, in
     return -1;
   return with_team_size(K, [&](auto k) {
     careers_add_k<decltype(k)::value>(rec, rows, W, M, base, P, track, score, modes, table);
+  }) ? 0 : -1;
+}
+
+// K17: every game in (match, slot) order, added to its player's row and to its cell
+template <int K>
+static void profiles_add_k(const int32_t* rec, const float* rows, int64_t W, const float* stats, int64_t M, int64_t P,
+                           int32_t track, int32_t score, uint32_t modes, const ProfileEdges& edges, int32_t* table,
+                           int64_t* cells) {
+  constexpr int S = 2 * K;
+  for (int64_t m = 0; m < M; ++m) {
+    const int32_t* r = rec + m * (S + 2);
+    const uint32_t mask = career_mask<K>(r, P, modes);
+    if (!mask) continue;  // the row is only read for a candidate
+    uint32_t row[5 * S + 2];
+    memcpy(row, rows + m * W, sizeof(row));
+    if (select_row_status<K>(row) != kRated) continue;
+    const int f = career_field(track), mode = meta_mode((uint32_t)r[S]);
+    for (int j = 0; j < S; ++j) {
+      if (!((mask >> j) & 1u)) continue;
+      int32_t bad = 0;
+      const ProfileRun g = profile_game(stats + (m * S + j) * kProfileStats, profile_won<K>(r, j), bad);
+      profile_row_add(table + (int64_t)r[j] * kProfileWords, g);
+      const float s = ladder_score(ladder_float(row[f * S + j]), ladder_float(row[(f + 1) * S + j]), score);
+      profile_cell_add(edges, mode, s, g, bad, [&](int c, int64_t v) { cells[c] += v; });
+    }
+  }
+}
+
+int host_profiles_add(int K, const int32_t* rec, const float* rows, int64_t W, const float* stats, int64_t M,
+                      int64_t P, int track, int score, uint32_t modes, const float* edges, int n_edges,
+                      int32_t* table, int64_t* cells) {
+  if (W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll || (track != kCareerShared && track != kCareerMode) ||
+      (score != kLadderConservative && score != kLadderMu) || (modes & ~kCareerAllModes) || n_edges < 0 ||
+      n_edges > kProfileMaxEdges)
+    return -1;
+  ProfileEdges pe;
+  pe.n = n_edges;
+  for (int i = 0; i < kProfileMaxEdges; ++i) pe.e[i] = i < n_edges ? edges[i] : 0.0f;
+  for (int i = 0; i < n_edges; ++i)
+    if (!isfinite(pe.e[i]) || (i > 0 && !(pe.e[i - 1] < pe.e[i]))) return -1;
+  return with_team_size(K, [&](auto k) {
+    profiles_add_k<decltype(k)::value>(rec, rows, W, stats, M, P, track, score, modes, pe, table, cells);
   }) ? 0 : -1;
 }
 

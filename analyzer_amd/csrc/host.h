@@ -86,6 +86,12 @@ using PairMap = std::map<int64_t, std::array<int32_t, 4>>;
 int host_pairs_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
                    const uint32_t* bitmap, PairMap& table);
 void host_pairs_merge(const int64_t* keys, const int32_t* counts, int64_t n, PairMap& table);
+// K17 host mirror (profile_core.h): the games of rec [M][2K+2] joined with rows [M][W] and stats
+// [M][2K][8], each added to its row of table [P][kProfileWords] and its cell of cells
+// [profile_table_words(n_edges + 1)], bit-identical to the device.  -1: bad arguments.
+int host_profiles_add(int K, const int32_t* rec, const float* rows, int64_t W, const float* stats, int64_t M,
+                      int64_t P, int track, int score, uint32_t modes, const float* edges, int n_edges,
+                      int32_t* table, int64_t* cells);
 // K12 host mirror (matchmake_core.h); out / records as launch_preview / launch_balance /
 // launch_queue_keys (kernels.h) lay them out; attrs may be null.  preview runs rate's own
 // fp64 path (status and quality are the bits host_rate writes); balance chooses the split in

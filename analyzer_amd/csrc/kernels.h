@@ -164,6 +164,24 @@ int launch_pair_emit(const uint32_t* a, const uint32_t* b, const uint32_t* vals,
                      const int32_t* src, const int64_t* offsets, int64_t U, int64_t* keys, int32_t* counts,
                      hipStream_t s);
 
+// K17 profiles (profile.hip, profile_core.h): one window rec [M][2K+2] joined with its packed rows
+// [M][W] (alignment as for K10) and its stat vectors stats [M][2K][8] fp32 (16-B aligned), M * 2K
+// <= kMaxSlots.  profile_keys writes per slot i = m * 2K + j the sort key (the player of a game,
+// else P) and vals[i] = i | won << 31, and adds every game to its cell of the baseline table cells
+// [profile_table_words(n_edges + 1)] int64 (edges: n_edges <= kProfileMaxEdges finite ascending
+// host floats); the pairs are sorted with launch_radix_sort_pairs on bit_length(P) bits;
+// profile_fold takes the sorted pairs [n = M * 2K] and adds every player's run to its row of table
+// [P][kProfileWords] (16-B aligned; edges: profile_edge_bytes(n) bytes, 16-B aligned).  track:
+// CareerTrack; score: LadderScore; modes: bit per mode.  Everything is stream-ordered and only
+// reads rec, rows and stats.
+constexpr int kProfileTile = 4096;  // sorted elements per workgroup of the fold
+size_t profile_edge_bytes(int64_t n);
+int launch_profile_keys(int K, const int32_t* rec, const float* rows, int64_t W, const float* stats, int64_t M,
+                        int64_t P, int track, int score, uint32_t modes, const float* edges, int n_edges,
+                        uint32_t* keys, uint32_t* vals, int64_t* cells, hipStream_t s);
+int launch_profile_fold(const uint32_t* keys, const uint32_t* vals, const float* stats, int64_t n, int K, int64_t P,
+                        int32_t* table, void* edges, hipStream_t s);
+
 // Stable LSD radix sort of (key, value) pairs on the low ``bits`` key bits
 // (radix_sort.hip).  Ping-pongs between the two buffer pairs; *result_in_alt
 // says which holds the result.  ws: radix_sort_workspace_bytes(n) bytes (256 counts per

@@ -4,5 +4,6 @@ from .ladder import Ladder, build_ladder  # noqa: F401
 from .careers import CareerTable  # noqa: F401
 from .scorecard import Scorecard, match_priors  # noqa: F401
 from .pairs import PairTable  # noqa: F401
+from .profiles import ProfileTable  # noqa: F401
 from .matchmake import (Balanced, Preview, balance_lobbies, fill_winners, make_lobbies,  # noqa: F401
                         preview_matches)

@@ -1,0 +1,487 @@
+"""Shared cases of the profile tests (test_profiles.py on the CPU, test_profiles_gpu.py on the
+device): a numpy oracle of the two tables of ``ProfileTable`` written from the definition of
+a game, a stat term and a bracket (``np.add.at`` on int64; nothing of csrc/profile_core.h),
+the windows it is checked on, and the checks that run the same way on either device.
+
+Every check is ``torch.equal`` on the whole player table and the whole cell table."""
+import functools
+import json
+import os
+import subprocess
+import sys
+from fractions import Fraction
+
+import numpy as np
+import torch
+
+from analyzer_amd.config import MODES
+from analyzer_amd.ops.native import native
+from analyzer_amd.ops.profiles import ProfileTable, baseline_line, default_edges, profile_lines, synthetic_profile
+from analyzer_amd.ops.rate import AFK, INVALID_ROSTERS, RATED, BatchRater, RateResult
+from analyzer_amd.ops.synth import RosterSpec, StreamSpec, make_roster, make_stream
+from analyzer_amd.ops.telemetry import TelemetrySpec, allocate_stats, make_telemetry
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TILE = 4096  # sorted elements per workgroup of the fold (csrc/kernels.h kProfileTile; checked below)
+NAN, INF = float("nan"), float("inf")
+TWO30 = float(2 ** 30)
+ABOVE_TWO30 = float(np.nextafter(np.float32(2 ** 30), np.float32(INF)))
+POISON = (NAN, 1.0e9, INF, -5.0, TWO30, -INF, 3.0e38, 777.0)  # the stats of slots that are no game
+
+
+def check_tile():
+    assert int(native().PROFILE_TILE) == TILE and int(native().PROFILE_WORDS) == 20
+
+
+# ------------------------------------------------------------------ the oracle
+def game_mask(rec, rows, P, modes=None):
+    """bool [M, 2K]: the slots that are games, and what the oracle needs next to them."""
+    r = rec.numpy().astype(np.int64)
+    S = r.shape[1] - 2
+    K = S // 2
+    ids = r[:, :S]
+    m0, m1 = r[:, S] & 0xFFFFFFFF, r[:, S + 1] & 0xFFFFFFFF
+    mode, n0, n1 = m0 & 0xFF, (m0 >> 8) & 0xFF, (m0 >> 16) & 0xFF
+    j = np.arange(S)
+    occupied = np.where(j < K, j, j - K)[None, :] < np.where(j < K, n0[:, None], n1[:, None])
+    allowed = list(range(len(MODES))) if modes is None else [MODES.index(m) for m in modes]
+    status = rows.view(torch.int32).numpy()[:, 5 * S + 1] & 0xFF
+    match_ok = np.isin(mode, allowed) & (status == RATED)
+    game = occupied & (ids >= 0) & (ids < P) & match_ok[:, None]
+    won = np.where(j[None, :] < K, m1[:, None] & 1, (m1[:, None] >> 1) & 1).astype(bool)
+    return game, ids, np.broadcast_to(mode[:, None], ids.shape), won
+
+
+def profile_ref(rec, rows, stats, P, track="shared", score="conservative", modes=None, edges=None):
+    """(player table [P, 20] int32, cell table [6 * B * 2 * 9 + 2] int64) of one window."""
+    game, ids, mode, won = game_mask(rec, rows, P, modes)
+    S = ids.shape[1]
+    f = 0 if track == "shared" else 3
+    w = rows.numpy()
+    mu, sigma = w[:, f * S:(f + 1) * S], w[:, (f + 1) * S:(f + 2) * S]
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = (mu if score == "mu" else mu - sigma) + np.float32(0)  # fp32
+        x = stats.numpy()
+        good = np.isfinite(x) & (x >= 0) & (x <= np.float32(2 ** 30))
+        terms = np.rint(np.where(good, x, 0).astype(np.float64) * 256).astype(np.int64)
+    e = np.asarray(default_edges() if edges is None else edges, dtype=np.float32)
+    B = len(e) + 1
+    bracket = (e[None, None, :] <= s[:, :, None]).sum(axis=2)
+    lost = np.isnan(s)
+    games, wins, sums = np.zeros(P, np.int64), np.zeros(P, np.int64), np.zeros((P, 8), np.int64)
+    np.add.at(games, ids[game], 1)
+    np.add.at(wins, ids[game], won[game].astype(np.int64))
+    np.add.at(sums, ids[game], terms[game])
+    table = np.zeros((P, 20), np.int64)
+    table[:, 0], table[:, 1] = games, wins
+    table[:, 4::2], table[:, 5::2] = sums & 0xFFFFFFFF, (sums >> 32) & 0xFFFFFFFF
+    cells = np.zeros((len(MODES), B, 2, 9), np.int64)
+    sel = game & ~lost
+    np.add.at(cells, (mode[sel], bracket[sel], won[sel].astype(np.int64)),
+              np.concatenate([np.ones((int(sel.sum()), 1), np.int64), terms[sel]], axis=1))
+    counters = np.array([int((~good)[game].sum()), int((game & lost).sum())], np.int64)
+    return (torch.from_numpy(table.astype(np.uint32).view(np.int32).copy()),
+            torch.from_numpy(np.concatenate([cells.reshape(-1), counters])))
+
+
+# ------------------------------------------------------------------ windows
+def random_window(K, M, P, seed, games=None, other=0.0, span=7, nan=0.0, modes=6, results=4):
+    """(rec, rows): M matches of random players of [0, P) with scores on a small integer grid
+    (shared mu -3..3 with -0.0, sigma 0..2; mode-track mu 0..600, sigma 1..61), random modes
+    and winner bits (none, one, both); ``other``: the share of matches that are AFK, invalid,
+    unsupported or failed; ``nan``: the share of NaN mu values.  ``games``: empty slots of the
+    last matches until exactly that many slots are occupied."""
+    g = torch.Generator().manual_seed(seed)
+    S, W = 2 * K, RateResult.row_floats(K)
+    ri = lambda hi, *shape: torch.randint(hi, shape, generator=g)  # noqa: E731
+    n0, n1 = torch.full((M,), K), torch.full((M,), K)
+    free = 0 if games is None else M * S - games
+    for m in reversed(range(M)):
+        if free <= 0:
+            break
+        drop = min(free, S - 1)
+        free -= drop
+        n1[m] = K - min(drop, K)
+        n0[m] = K - (drop - (K - int(n1[m])))
+    rec = torch.zeros((M, S + 2), dtype=torch.int64)
+    rec[:, :S] = ri(P, M, S)
+    rec[:, S] = ri(modes, M) | (n0 << 8) | (n1 << 16) | (2 << 24)
+    rec[:, S + 1] = ri(results, M) if results == 4 else torch.full((M,), results)
+    status = torch.full((M,), RATED)
+    odd = torch.tensor([AFK, INVALID_ROSTERS, 3, 7, 255])[ri(5, M)]
+    status = torch.where(torch.rand(M, generator=g) < other, odd, status)
+    rows = torch.full((M, W), 12345.0, dtype=torch.float32)
+    rows[:, 0:S] = (ri(span, M, S) - span // 2).to(torch.float32) * -1.0
+    rows[:, S:2 * S] = ri(3, M, S).to(torch.float32)
+    rows[:, 2 * S:3 * S] = 0.0
+    rows[:, 3 * S:4 * S] = ri(span, M, S) * 100.0
+    rows[:, 4 * S:5 * S] = ri(span, M, S) * 10.0 + 1.0
+    for f in (0, 3):
+        holes = torch.rand((M, S), generator=g) < nan
+        rows[:, f * S:(f + 1) * S][holes] = NAN
+    rows[:, 5 * S] = 0.5
+    rows.view(torch.int32)[:, 5 * S + 1] = (status | 0x5A5A00).to(torch.int32)
+    return rec.to(torch.int32), rows
+
+
+def random_stats(M, S, seed, bad=0.02):
+    """fp32 [M, S, 8]: whole units of 1/256, exact ties (n + 0.5) / 256, sixteenths of a unit,
+    values up to 2^26 (a few hundred of them pass 32 bits of sum), zeros, and a share ``bad``
+    of NaN, infinities, negative values and values above 2^30."""
+    g = torch.Generator().manual_seed(seed + 1000)
+    i = torch.randint(1 << 16, (M, S, 8), generator=g).to(torch.float64)
+    kind = torch.randint(5, (M, S, 8), generator=g)
+    x = torch.zeros((M, S, 8), dtype=torch.float64)
+    for k, v in enumerate((i / 256, (i + 0.5) / 256, i / 4096, i * 1024.0)):
+        x = torch.where(kind == k, v, x)
+    x = x.to(torch.float32)
+    off = torch.tensor([NAN, INF, -INF, -1.0, ABOVE_TWO30, 3.0e38, -2.0 ** -140], dtype=torch.float32)
+    return torch.where(torch.rand((M, S, 8), generator=g) < bad, off[torch.randint(7, (M, S, 8), generator=g)], x)
+
+
+def poison(stats, game):
+    """The stats of the slots that are no game overwritten with NaN and huge values."""
+    bad = torch.tensor(POISON, dtype=torch.float32).repeat(stats.shape[0], stats.shape[1], 1)
+    return torch.where(torch.from_numpy(game.copy())[:, :, None], stats, bad)
+
+
+def with_stats(rec, rows, P, opt, seed, bad=0.02):
+    stats = random_stats(rec.shape[0], rec.shape[1] - 2, seed, bad)
+    return rec, rows, poison(stats, game_mask(rec, rows, P, opt.get("modes"))[0]), P, opt
+
+
+def window(K, matches):
+    """(rec, rows, stats) from a list of dicts: ``ids`` [2K], and optionally ``mode`` (1), ``n0`` /
+    ``n1`` (K), ``meta1`` (1: roster 0 won), ``status`` (RATED), ``s_mu`` / ``s_sig`` / ``m_mu`` /
+    ``m_sig`` (per slot or one number) and ``stats`` (per slot a list of 8, or one list for all)."""
+    S, W = 2 * K, RateResult.row_floats(K)
+    rec = torch.zeros((len(matches), S + 2), dtype=torch.int64)
+    rows = torch.full((len(matches), W), 12345.0, dtype=torch.float32)
+    stats = torch.zeros((len(matches), S, 8), dtype=torch.float32)
+    for m, c in enumerate(matches):
+        rec[m, :S] = torch.tensor(c["ids"])
+        rec[m, S] = c.get("mode", 1) | (c.get("n0", K) << 8) | (c.get("n1", K) << 16) | (2 << 24)
+        rec[m, S + 1] = c.get("meta1", 1)
+        for f, name in enumerate(("s_mu", "s_sig", "delta", "m_mu", "m_sig")):
+            v = c.get(name, (1500.0, 300.0, 0.0, 1400.0, 250.0)[f])
+            rows[m, f * S:(f + 1) * S] = torch.tensor(v if isinstance(v, (list, tuple)) else [v] * S,
+                                                      dtype=torch.float32)
+        rows[m, 5 * S] = 0.5
+        rows.view(torch.int32)[m, 5 * S + 1] = c.get("status", RATED) | 0x5A5A00
+        v = c.get("stats", [1.0] * 8)
+        stats[m] = torch.tensor(v if isinstance(v[0], (list, tuple)) else [v] * S, dtype=torch.float32)
+    return rec.to(torch.int32), rows, stats
+
+
+# the hand-built stat values of case "values", one game each, and what each adds (None: bad)
+def _term(x):
+    x32 = float(np.float32(x))
+    if x32 != x32 or x32 in (INF, -INF) or x32 < 0 or x32 > TWO30:
+        return None
+    return int(round(Fraction(x32) * 256))  # exact product, ties to even
+
+
+VALUES = [0.0, -0.0, 2.0 ** -10, 2.0 ** -9 - 2.0 ** -30, 0.5 / 256, 0.5 / 256 + 2.0 ** -30, 1.5 / 256, 2.5 / 256,
+          3.5 / 256, 1000000.5 / 256, 1000001.5 / 256, 0.7 / 256, 1.0 / 256, 12.25, TWO30,
+          float(np.nextafter(np.float32(2 ** 30), np.float32(0))), ABOVE_TWO30, 2.0 ** 31, 3.0e38, -1.0, -2.0 ** -149,
+          -1.0e30, NAN, INF, -INF, 255.99609375, 4194303.998046875]
+assert [_term(v) for v in VALUES[:9]] == [0, 0, 0, 0, 0, 1, 2, 2, 4] and _term(1000000.5 / 256) == 1000000
+assert _term(1000001.5 / 256) == 1000002 and _term(TWO30) == 2 ** 38 and _term(ABOVE_TWO30) is None
+VALUES_BAD = sum(1 for v in VALUES if _term(v) is None)
+assert VALUES_BAD == 9
+
+EDGE_SCORES = [(10.0, 0.0, 1), (float(np.nextafter(np.float32(10), np.float32(0))), 0.0, 0), (20.0, 0.0, 2),
+               (25.0, 5.0, 2), (NAN, 0.0, -1), (INF, 0.0, 2), (-INF, 0.0, 0), (INF, INF, -1), (-0.0, 0.0, 0),
+               (30.0, 20.0 + 2.0 ** -19, 0), (5.0, NAN, -1)]  # (mu, sigma, bracket under edges 10, 20)
+
+HAND_P = 9
+GUARD_MODES = ("ranked", "blitz")
+
+
+def guard_matches():
+    """K = 2, P = 9: ids -1, P and 2^31 - 1 in occupied slots of rated rows, slots beyond n0 / n1,
+    unselected modes and non-rated statuses around a few games of players 0..3."""
+    X = 8
+    ms = [{"ids": [0, X, X, 1], "mode": 1}, {"ids": [-1, 9, 2 ** 31 - 1, -5], "mode": 1},
+          {"ids": [X, -1, 100, 2], "mode": 2, "meta1": 2}, {"ids": [1, X, X, X], "mode": 1, "n0": 1, "n1": 0},
+          {"ids": [3, 3, 3, 3], "mode": 1, "n0": 0, "n1": 1, "meta1": 2}]
+    ms += [{"ids": [0, 1, 2, 3], "mode": m} for m in (0, 3, 4, 5, 6, 255)]
+    ms += [{"ids": [0, 1, 2, 3], "mode": 1, "status": st} for st in (AFK, INVALID_ROSTERS, 3, 4, 5, 6, 7, 8, 255)]
+    ms += [{"ids": [2, X, 0, X], "mode": 2, "meta1": 3}, {"ids": [X, 9, X, 2 ** 31 - 1], "mode": 1, "meta1": 0}]
+    return ms
+
+
+def api_matches():
+    """K = 1, P = 9, edges (10, 20), score mu - sigma with sigma 0: every number of
+    ``check_api`` is worked out from this list.  Stats: kills k, the rest 0 except events 1."""
+    def game(a, b, mode, mu_a, mu_b, ka, kb, meta1=1):
+        return {"ids": [a, b], "mode": mode, "meta1": meta1, "s_mu": [mu_a, mu_b], "s_sig": 0.0,
+                "stats": [[ka, 0, 0, 0, 0, 0, 0, 1], [kb, 0, 0, 0, 0, 0, 0, 1]]}
+    return [game(0, 1, 1, 5.0, 15.0, 2.0, 4.0), game(0, 2, 1, 5.0, 25.0, 4.0, 1.0),
+            game(1, 0, 0, 15.0, 12.0, 6.0, 3.5, meta1=2), game(3, 0, 1, NAN, 7.0, 9.0, 0.25),
+            game(4, 4, 1, 10.0, 20.0, 1.0, 2.0)]
+
+
+STITCH = (5, 52_429, 37)  # K, M, P of the window whose fold leaves 129 tiles
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """(rec, rows, stats, P, options of ProfileTable) of a named case, built once."""
+    kind, _, arg = name.partition(":")
+    grid = {"edges": (-3.0, -1.0, 0.0, 2.0)}  # the shared conservative scores are the integers -5..3
+    if kind == "tile":  # tile:K:games -- games just below / at / above one tile and above two
+        K, games = (int(x) for x in arg.split(":"))
+        M = -(-games // (2 * K))
+        rec, rows = random_window(K, M, 37, seed=K * 10007 + games, games=games)
+        assert int(game_mask(rec, rows, 37)[0].sum()) == games
+        return with_stats(rec, rows, 37, grid, seed=games + K)
+    if kind == "alias":  # one player in both slots of every match
+        M = TILE + TILE // 2
+        rec, rows = random_window(1, M, 1, seed=3)
+        return with_stats(rec, rows, 1, grid, seed=4)
+    if kind == "few":  # few:P -- every run crosses tile edges
+        rec, rows = random_window(2, 2500, int(arg), seed=int(arg))
+        return with_stats(rec, rows, int(arg), grid, seed=int(arg))
+    if kind == "stitch":  # more than 256 edges: the stitch kernel runs a second iteration
+        K, M, P = STITCH
+        rec, rows = random_window(K, M, P, seed=77)
+        game = game_mask(rec, rows, P)[0]
+        keys = np.sort(rec[:, :2 * K].numpy().reshape(-1))
+        assert bool(game.all()) and len(keys) == 524_290 and 2 * -(-len(keys) // TILE) == 258
+        # edge 255 ends tile 127, edge 256 begins tile 128: one player's run crosses the iterations,
+        # and every player is cut by more than one tile edge
+        assert keys[128 * TILE - 1] == keys[128 * TILE] and np.bincount(keys).min() > 2 * TILE
+        return with_stats(rec, rows, P, grid, seed=78)
+    if kind == "mixed":  # every kind of match, NaN scores among them
+        rec, rows = random_window(3, 900, 50, seed=5, other=0.3, nan=0.05)
+        return with_stats(rec, rows, 50, grid, seed=6)
+    if kind == "onecell":  # one mode, every slot wins, every score in one bracket
+        rec, rows = random_window(2, 700, 30, seed=8, modes=1, results=3)
+        return with_stats(rec, rows, 30, {"edges": (-100.0, 100.0)}, seed=9)
+    if kind == "allcells":  # B = 32 and games in all 6 x 32 x 2 cells: the mu scores are 0 .. 31
+        rec, rows = random_window(3, 4000, 200, seed=10, span=32)
+        rows[:, 0:6] = rows[:, 0:6] * -1.0 + 16.0
+        opt = {"score": "mu", "edges": tuple(b + 0.5 for b in range(31))}
+        return with_stats(rec, rows, 200, opt, seed=11)
+    if kind == "nobracket":  # B = 1
+        rec, rows = random_window(3, 300, 40, seed=12, other=0.2, nan=0.1)
+        return with_stats(rec, rows, 40, {"edges": ()}, seed=13)
+    if kind == "edges":  # scores on an edge, just below it, NaN and infinite
+        ms = [{"ids": [i % 4, 4 + i % 3], "s_mu": [mu, 15.0], "s_sig": [sg, 0.0], "meta1": 1 + i % 2}
+              for i, (mu, sg, _) in enumerate(EDGE_SCORES)]
+        return window(1, ms) + (7, {"edges": (10.0, 20.0)})
+    if kind == "values":  # the hand-built stat values, one per game of player 0
+        vals = VALUES + [0.0] * (-len(VALUES) % 8)
+        ms = [{"ids": [0, 1], "stats": [vals[a:a + 8], [NAN] * 8], "n1": 0} for a in range(0, len(vals), 8)]
+        return window(1, ms) + (2, {"edges": ()})
+    if kind == "guards":
+        rec, rows, stats = window(2, guard_matches())
+        opt = {"modes": GUARD_MODES}
+        return rec, rows, poison(stats, game_mask(rec, rows, HAND_P, GUARD_MODES)[0]), HAND_P, opt
+    if kind == "api":
+        return window(1, api_matches()) + (HAND_P, {"edges": (10.0, 20.0)})
+    if kind == "opt":  # opt:track:score:modes
+        track, score, modes = arg.split(":")
+        rec, rows = random_window(3, 300, 40, seed=21, other=0.2, nan=0.03)
+        opt = {"track": track, "score": score, "modes": tuple(modes.split("+")) if modes else None,
+               "edges": grid["edges"] if track == "shared" else (99.0, 250.0, 400.5)}
+        return with_stats(rec, rows, 40, opt, seed=22)
+    if kind == "split":
+        rec, rows = random_window(2, 240, 11, seed=33, other=0.2, nan=0.05)
+        return with_stats(rec, rows, 11, grid, seed=34)
+    if kind == "real":
+        return realistic()
+    raise KeyError(name)
+
+
+REAL = (3, 3000, 4000)  # K, M, P of the realistic case
+
+
+@functools.lru_cache(maxsize=None)
+def realistic():
+    """A synthetic roster, stream (skewed activity, every kind of match) and telemetry, rated
+    with telemetry by the host mirror once; default edges."""
+    K, M, P = REAL
+    roster = make_roster(RosterSpec(num_players=P, seed=41))
+    rec = make_stream(StreamSpec(team_size=K, seed=42, p_afk=0.05, p_unsupported=0.05, p_uneven=0.1, skew=2), M, P, K=K)
+    tel = make_telemetry(TelemetrySpec(seed=43, min_events=20, max_events=60), rec, K)
+    stats = allocate_stats(M, K, "cpu")
+    res = BatchRater().rate(roster, rec, K, telemetry=(tel.evoff, tel.events, stats))
+    return rec, res.packed, stats, P, {}
+
+
+TILE_CASES = ["tile:%d:%d" % (K, n) for K in (1, 2, 3, 4, 5) for n in (TILE - 1, TILE, TILE + 1, 2 * TILE + 3)]
+LONG_CASES = ["alias", "few:2", "few:3", "stitch"]
+CELL_CASES = ["onecell", "allcells", "nobracket", "edges"]
+OTHER_CASES = ["mixed", "values", "guards", "api", "real", "opt:shared:conservative:ranked", "opt:mode:conservative:",
+               "opt:shared:mu:", "opt:mode:mu:casual+blitz", "split"]
+
+
+@functools.lru_cache(maxsize=None)
+def expected(name):
+    rec, rows, stats, P, opt = case(name)
+    return profile_ref(rec, rows, stats, P, **opt)
+
+
+def fold(name, device, pieces=None, **kw):
+    """The table of a case on ``device``: its window added in one piece, or the ``pieces``
+    (a, b) of it in the order given."""
+    rec, rows, stats, P, opt = case(name)
+    table = ProfileTable(P, device, **opt)
+    for k, v in kw.items():
+        setattr(table, k, v)
+    for a, b in pieces if pieces is not None else [(0, rec.shape[0])]:
+        table.add(rec[a:b].to(device), rows[a:b].to(device), stats[a:b].to(device))
+    return table
+
+
+@functools.lru_cache(maxsize=None)
+def host_tables(name):
+    t = fold(name, "cpu")
+    return t.table, t.cells
+
+
+def assert_tables(table, want, what):
+    got_t, got_c = table.table.cpu(), table.cells.cpu()
+    assert got_t.dtype == torch.int32 and got_c.dtype == torch.int64
+    rows = (got_t != want[0]).any(dim=1).nonzero().reshape(-1)[:5].tolist()
+    assert torch.equal(got_t, want[0]), (what, "players", rows, got_t[rows].tolist(), want[0][rows].tolist())
+    words = (got_c != want[1]).nonzero().reshape(-1)[:8].tolist()
+    assert torch.equal(got_c, want[1]), (what, "cells", words, got_c[words].tolist(), want[1][words].tolist())
+
+
+def check_case(name, device):
+    table = fold(name, device)
+    P = case(name)[3]
+    assert tuple(table.table.shape) == (P, 20) and table.cells.numel() == 6 * table.brackets * 2 * 9 + 2
+    assert table.table.device.type == torch.device(device).type == table.cells.device.type
+    assert_tables(table, expected(name), name)
+    if torch.device(device).type != "cpu":
+        assert_tables(table, host_tables(name), name + " (host mirror)")
+    return table
+
+
+# ------------------------------------------------------------------ checks
+def check_cells(device):
+    one = check_case("onecell", device).baselines()["games"]
+    assert int((one > 0).sum()) == 1 and int(one[0, 1, 1]) == int(one.sum()) > 2000
+    every = check_case("allcells", device)
+    assert every.brackets == 32 and bool((every.baselines()["games"] > 0).all())
+    flat = check_case("nobracket", device)
+    assert flat.brackets == 1 and flat.unbracketed > 20 and tuple(flat.baselines()["games"].shape) == (6, 1, 2)
+    edged = check_case("edges", device)
+    want = [b for _, _, b in EDGE_SCORES]
+    assert edged.unbracketed == want.count(-1) == 3
+    with np.errstate(invalid="ignore"):
+        scores = [float(np.float32(mu) - np.float32(sg)) for mu, sg, _ in EDGE_SCORES]
+    assert edged.bracket_of(scores).tolist() == want
+    games = edged.baselines()["games"].sum(dim=(0, 2)).tolist()  # the partners all score 15: bracket 1
+    assert games == [want.count(0), want.count(1) + len(want), want.count(2)]
+    assert int(edged.columns()["games"].sum()) == 2 * len(want)  # a game without a bracket is still a game
+
+
+def check_stat_values(device):
+    table = check_case("values", device)
+    terms = [_term(v) for v in VALUES]
+    sums = table.columns()["sums"][0].tolist()
+    assert sums == [sum(t or 0 for t in terms[k::8]) for k in range(8)]
+    assert table.bad == VALUES_BAD and int(table.columns()["games"][1]) == 0  # the NaNs of slot 1 are no game's
+
+
+def check_guards(device):
+    """Ids -1, P and 2^31 - 1, slots beyond n0 / n1, unselected modes, non-rated statuses, all
+    with poisoned stats: neither table moves for them, nor do the rows next to the table."""
+    rec, rows, stats, P, opt = case("guards")
+    game = game_mask(rec, rows, P, GUARD_MODES)[0]
+    assert int(game.sum()) == 14 and not bool(np.isfinite(stats.numpy()[~game]).all())
+    table = ProfileTable(P, device, **opt)
+    big = torch.full((P + 2, 20), 0x55AA55, dtype=torch.int32, device=device)
+    big[1:P + 1] = table.table
+    table.table = big[1:P + 1]
+    table.add(rec.to(device), rows.to(device), stats.to(device))
+    assert_tables(table, expected("guards"), "guards")
+    assert bool((big[0] == 0x55AA55).all()) and bool((big[P + 1] == 0x55AA55).all())
+    assert table.bad == 0 and table.unbracketed == 0
+    cols = table.columns()
+    # the bystander 8 plays 7 of the 14 games; every game's stats are eight 1.0
+    assert cols["games"].tolist() == [2, 2, 2, 1, 0, 0, 0, 0, 7]
+    assert cols["wins"].tolist() == [2, 1, 2, 1, 0, 0, 0, 0, 3]
+    assert int(table.baselines()["games"].sum()) == 14 and int(cols["sums"].sum()) == 14 * 8 * 256
+
+
+def check_invariance(device):
+    M = case("split")[0].shape[0]
+    whole = fold("split", device)
+    assert_tables(whole, expected("split"), "split")
+    want = (whole.table.cpu(), whole.cells.cpu())
+    assert whole.unbracketed > 0 and whole.bad > 0
+    cuts = [(0, 1), (1, 77), (77, 78), (78, M - 1), (M - 1, M)]
+    assert_tables(fold("split", device, cuts), want, "cuts")
+    assert_tables(fold("split", device, cuts[::-1]), want, "reversed")
+    assert_tables(fold("split", device, [(0, 100)]).merge(fold("split", device, [(100, M)])), want, "merge")
+    assert_tables(fold("split", device), want, "second run")
+    assert_tables(fold("split", device, [(0, M), (5, 5)]), want, "M = 0")  # an empty window adds nothing
+    assert_tables(fold("split", device, max_slots=4 * 50 + 3), want, "chunks of 50 matches")
+    assert_tables(fold("alias", device, max_slots=2 * 1000 + 1), expected("alias"), "alias in chunks")  # 64-bit sums
+    assert int(fold("alias", device).columns()["sums"].max()) > 1 << 32
+
+
+def check_realistic(device):
+    table = check_case("real", device)
+    base = table.baselines()["games"]
+    assert int((base.sum(dim=(0, 2)) > 0).sum()) >= 3 and int((base.sum(dim=(1, 2)) > 0).sum()) >= 2
+    games = table.columns()["games"]
+    assert int((games == 0).sum()) > 50 and int((games >= 10).sum()) > 50
+    assert int(table.columns()["sums"][:, 7].sum()) > 20 * int(games.sum())  # events: the telemetry is there
+    assert table.bad == 0
+
+
+def check_api(device):
+    """``api_matches``: player 0 plays 4 games (wins 3), kills 2 + 4 + 3.5 + 0.25."""
+    t = check_case("api", device)
+    look = {k: v.cpu() for k, v in t.lookup([0, 3, 8, 4]).items()}
+    assert look["games"].tolist() == [4, 1, 0, 2] and look["wins"].tolist() == [3, 1, 0, 1]
+    assert look["sums"][:, 0].tolist() == [int(9.75 * 256), 9 * 256, 0, 3 * 256] and look["sums"].dtype == torch.int64
+    assert look["win_rate"][:2].tolist() == [0.75, 1.0]
+    assert look["per_game"][0].tolist() == [9.75 / 4, 0, 0, 0, 0, 0, 0, 1.0]
+    assert bool(torch.isnan(look["win_rate"][2])) and bool(torch.isnan(look["per_game"][2]).all())
+    cols = t.columns()
+    assert cols["games"].tolist() == [4, 2, 1, 1, 2, 0, 0, 0, 0] and tuple(cols["sums"].shape) == (9, 8)
+    base = {k: v.cpu() for k, v in t.baselines().items()}
+    assert base["edges"].tolist() == [10.0, 20.0] and tuple(base["sums"].shape) == (6, 3, 2, 8)
+    # mode 1 bracket 0: player 0 at 5.0 won twice (kills 2, 4) and at 7.0 lost (0.25)
+    assert base["games"][1, 0].tolist() == [1, 2] and base["sums"][1, 0, 1, 0].item() == 6 * 256
+    assert base["sums"][1, 0, 0, 0].item() == 64
+    # mode 1 bracket 1: player 1 at 15.0 lost (4), player 4 at 10.0 won (1); bracket 2: 25.0 and 20.0 lost
+    assert base["games"][1, 1].tolist() == [1, 1] and base["games"][1, 2].tolist() == [2, 0]
+    # mode 0 bracket 1: player 1 at 15.0 lost (6), player 0 at 12.0 won (3.5)
+    assert base["games"][0, 1].tolist() == [1, 1] and base["per_game"][0, 1, 1, 0].item() == 3.5
+    assert int(base["games"].sum()) == 9 and t.unbracketed == 1 and t.bad == 0  # player 3's NaN game
+    assert bool(torch.isnan(base["per_game"][5]).all())
+    assert t.bracket_of([9.999, 10.0, 19.5, 20.0, NAN, INF, -INF]).tolist() == [0, 1, 1, 2, -1, 2, 0]
+    # bracket 1 over both modes and results: games 4, kills 4 + 1 + 6 + 3.5; player 1: (4 + 6) / 2
+    cmp = {k: v.cpu() for k, v in t.compare([1, 0, 5, 1], [15.0, 12.0, 15.0, NAN]).items()}
+    assert cmp["bracket"].tolist() == [1, 1, 1, -1]
+    assert cmp["baseline"][0, 0].item() == 14.5 / 4 and cmp["ratio"][0, 0].item() == 5.0 / (14.5 / 4)
+    assert cmp["ratio"][1, 0].item() == (9.75 / 4) / (14.5 / 4) and cmp["ratio"][0, 7].item() == 1.0
+    assert bool(torch.isnan(cmp["ratio"][2]).all()) and bool(torch.isnan(cmp["ratio"][3]).all())
+    ranked = t.compare([1], [15.0], modes=("ranked",))  # bracket 1 of mode 1: kills 4 + 1 over 2 games
+    assert ranked["baseline"][0, 0].item() == 2.5 and ranked["ratio"][0, 0].item() == 2.0
+
+
+def run_cli(device, *args):
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    return subprocess.run([sys.executable, "-m", "analyzer_amd.ops.profiles", "--device", device, *args],
+                          capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
+
+
+def check_cli(device):
+    ok = run_cli(device, "--matches", "600", "--players", "150", "--ids", "5,7,149")
+    assert ok.returncode == 0, ok.stderr
+    lines = [json.loads(ln) for ln in ok.stdout.splitlines() if ln.startswith("{")]
+    table = synthetic_profile(600, 150, 3, device)
+    assert lines == json.loads(json.dumps(profile_lines(table, [5, 7, 149]) + [baseline_line(table)]))
+    assert [ln["profile"] for ln in lines[:3]] == [5, 7, 149] and lines[0]["games"] > 0
+    assert sum(c["games"] for c in lines[3]["baselines"]) + lines[3]["unbracketed"] == int(
+        table.columns()["games"].sum()) > 2000
