@@ -935,6 +935,24 @@ Tensor tile_offsets(Tensor counts) {
   return offsets;
 }
 
+// The leading checks of careers_add and profiles_add: the window, its slots, P, the table
+// [P, words] int32 and the options -> (K, M)
+std::pair<int64_t, int64_t> check_fold_args(const Tensor& table, int64_t words, const Tensor& rec, const Tensor& rows,
+                                            int64_t P, int64_t track, int64_t score, int64_t modes, const char* what) {
+  const auto dev = table.device();
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, what, ": rec must be [M, 2K+2]");
+  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t M = check_window(rec, rows, K, dev, what);
+  check_slots(M, K, what);
+  TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, what, ": P must fit in int32");
+  check_rows(table, "table", P, words, dev, torch::kInt32);
+  TORCH_CHECK(track == ana::kCareerShared || track == ana::kCareerMode, what, ": unknown track ", track);
+  TORCH_CHECK(score == ana::kLadderConservative || score == ana::kLadderMu, what, ": unknown score ", score);
+  TORCH_CHECK(modes >= 0 && (modes & ~(int64_t)ana::kCareerAllModes) == 0, what,
+              ": the modes mask must name modes 0..5");
+  return {K, M};
+}
+
 // K13 (career.hip; host mirror host.cpp host_careers_add): folds the games of one window -- rec
 // [M, 2K+2] joined with its packed output rows [M, W], base the global index of match 0 -- into
 // the career table [P, 16] int32 in place (career_core.h).  Dispatches on the tensors' device;
@@ -942,17 +960,8 @@ Tensor tile_offsets(Tensor counts) {
 void careers_add(Tensor table, Tensor rec, Tensor rows, int64_t base, int64_t P, int64_t track, int64_t score,
                  int64_t modes) {
   const auto dev = table.device();
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "careers_add: rec must be [M, 2K+2]");
-  const int64_t K = (rec.size(1) - 2) / 2;
-  const int64_t M = check_window(rec, rows, K, dev, "careers_add");
-  check_slots(M, K, "careers_add");
-  TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "careers_add: P must fit in int32");
-  check_rows(table, "table", P, ana::kCareerWords, dev, torch::kInt32);
+  const auto [K, M] = check_fold_args(table, ana::kCareerWords, rec, rows, P, track, score, modes, "careers_add");
   TORCH_CHECK(base >= 0, "careers_add: base must be >= 0");
-  TORCH_CHECK(track == ana::kCareerShared || track == ana::kCareerMode, "careers_add: unknown track ", track);
-  TORCH_CHECK(score == ana::kLadderConservative || score == ana::kLadderMu, "careers_add: unknown score ", score);
-  TORCH_CHECK(modes >= 0 && (modes & ~(int64_t)ana::kCareerAllModes) == 0,
-              "careers_add: the modes mask must name modes 0..5");
   if (M == 0 || P == 0) return;
   if (!dev.is_cuda()) {
     TORCH_CHECK(ana::host_careers_add((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, base,
@@ -984,12 +993,7 @@ void careers_add(Tensor table, Tensor rec, Tensor rows, int64_t base, int64_t P,
 void profiles_add(Tensor table, Tensor cells, Tensor rec, Tensor rows, Tensor stats, int64_t P, int64_t track,
                   int64_t score, int64_t modes, Tensor edges) {
   const auto dev = table.device();
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "profiles_add: rec must be [M, 2K+2]");
-  const int64_t K = (rec.size(1) - 2) / 2;
-  const int64_t M = check_window(rec, rows, K, dev, "profiles_add");
-  check_slots(M, K, "profiles_add");
-  TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "profiles_add: P must fit in int32");
-  check_rows(table, "table", P, ana::kProfileWords, dev, torch::kInt32);
+  const auto [K, M] = check_fold_args(table, ana::kProfileWords, rec, rows, P, track, score, modes, "profiles_add");
   check(stats, "stats", torch::kFloat32, dev);
   TORCH_CHECK(stats.dim() == 3 && stats.size(0) == M && stats.size(1) == 2 * K && stats.size(2) == ana::kProfileStats,
               "profiles_add: stats must be [M, 2K, 8]");
@@ -1004,10 +1008,6 @@ void profiles_add(Tensor table, Tensor cells, Tensor rec, Tensor rows, Tensor st
   check(cells, "cells", torch::kInt64, dev);
   TORCH_CHECK(cells.numel() == ana::profile_table_words(n_edges + 1), "profiles_add: cells must hold ",
               ana::profile_table_words(n_edges + 1), " words");
-  TORCH_CHECK(track == ana::kCareerShared || track == ana::kCareerMode, "profiles_add: unknown track ", track);
-  TORCH_CHECK(score == ana::kLadderConservative || score == ana::kLadderMu, "profiles_add: unknown score ", score);
-  TORCH_CHECK(modes >= 0 && (modes & ~(int64_t)ana::kCareerAllModes) == 0,
-              "profiles_add: the modes mask must name modes 0..5");
   if (M == 0 || P == 0) return;
   if (!dev.is_cuda()) {
     TORCH_CHECK(ana::host_profiles_add((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1),

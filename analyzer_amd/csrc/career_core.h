@@ -46,6 +46,12 @@ enum CareerTrack : int32_t {
   kCareerMode = 1,    // (m_mu, m_sig)
 };
 
+// host side: the options of a K13 / K17 table as the launchers and host mirrors check them
+inline bool career_options_ok(int track, int score, uint32_t modes) {
+  return (track == kCareerShared || track == kCareerMode) && (score == kLadderConservative || score == kLadderMu) &&
+         !(modes & ~kCareerAllModes);
+}
+
 // a game's event, 8 B: word 0 the score bits, word 1 the quality term | win | status
 constexpr int kCareerEventWords = 2;
 constexpr uint32_t kCareerQualityMask = (1u << 25) - 1u;  // terms are 0..2^24

@@ -189,6 +189,21 @@ inline bool with_team_size(int K, F&& f) {
 }
 static_assert(kMaxTeamSize == 5, "with_team_size and early_status_k list the team sizes");
 
+// Host side, the argument checks of the launchers and host mirrors that take a window rec
+// [M][2K+2] joined with its packed rows [M][W] of P players: K in range, a row that holds the
+// five slot fields, quality and status, and a P that fits int32 ...
+inline bool window_ok(int K, int64_t W, int64_t M, int64_t P) {
+  return K >= 1 && K <= kMaxTeamSize && W >= 5 * 2 * K + 2 && M >= 0 && P >= 0 && P <= 0x7fffffffll;
+}
+// ... whose slots are sort values
+inline bool window_slots_ok(int K, int64_t W, int64_t M, int64_t P) {
+  return window_ok(K, W, M, P) && M * 2 * K <= kMaxSlots;
+}
+// ... and the n = M * 2K sorted slots of such a window
+inline bool sorted_slots_ok(int K, int64_t n, int64_t P) {
+  return K >= 1 && K <= kMaxTeamSize && n >= 0 && n <= kMaxSlots && n % (2 * K) == 0 && P >= 0 && P <= 0x7fffffffll;
+}
+
 // ---------------------------------------------------------------- RNG (K7)
 // Counter-based: every random number is a pure function of (seed, index,
 // field), so device and host generators produce bit-identical streams and any

@@ -384,10 +384,7 @@ static void careers_add_k(const int32_t* rec, const float* rows, int64_t W, int6
 
 int host_careers_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t base, int64_t P,
                      int track, int score, uint32_t modes, int32_t* table) {
-  if (W < 5 * 2 * K + 2 || M < 0 || base < 0 || P < 0 || P > 0x7fffffffll ||
-      (track != kCareerShared && track != kCareerMode) || (score != kLadderConservative && score != kLadderMu) ||
-      (modes & ~kCareerAllModes))
-    return -1;
+  if (!window_ok(K, W, M, P) || base < 0 || !career_options_ok(track, score, modes)) return -1;
   return with_team_size(K, [&](auto k) {
     careers_add_k<decltype(k)::value>(rec, rows, W, M, base, P, track, score, modes, table);
   }) ? 0 : -1;
@@ -421,9 +418,7 @@ static void profiles_add_k(const int32_t* rec, const float* rows, int64_t W, con
 int host_profiles_add(int K, const int32_t* rec, const float* rows, int64_t W, const float* stats, int64_t M,
                       int64_t P, int track, int score, uint32_t modes, const float* edges, int n_edges,
                       int32_t* table, int64_t* cells) {
-  if (W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll || (track != kCareerShared && track != kCareerMode) ||
-      (score != kLadderConservative && score != kLadderMu) || (modes & ~kCareerAllModes) || n_edges < 0 ||
-      n_edges > kProfileMaxEdges)
+  if (!window_ok(K, W, M, P) || !career_options_ok(track, score, modes) || n_edges < 0 || n_edges > kProfileMaxEdges)
     return -1;
   ProfileEdges pe;
   pe.n = n_edges;
@@ -468,7 +463,7 @@ static void pairs_add_k(const int32_t* rec, const float* rows, int64_t W, int64_
 
 int host_pairs_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
                    const uint32_t* bitmap, PairMap& table) {
-  if (W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll || (modes & ~kPairAllModes)) return -1;
+  if (!window_ok(K, W, M, P) || (modes & ~kPairAllModes)) return -1;
   return with_team_size(K, [&](auto k) {
     pairs_add_k<decltype(k)::value>(rec, rows, W, M, P, modes, bitmap, table);
   }) ? 0 : -1;
@@ -621,7 +616,7 @@ static void priors_add_k(const int32_t* rec, const float* rows, int64_t W, int64
 
 int host_priors_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, float* chain,
                     float* priors) {
-  if (W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll) return -1;
+  if (!window_ok(K, W, M, P)) return -1;
   return with_team_size(K, [&](auto k) { priors_add_k<decltype(k)::value>(rec, rows, W, M, P, chain, priors); })
              ? 0 : -1;
 }
@@ -661,7 +656,7 @@ static void score_add_k(const int32_t* rec, const float* priors, const float* ro
 int host_score_add(int K, const int32_t* rec, const float* priors, const float* rows, int64_t W, int64_t M,
                    const float* attrs, const float* vst, int64_t P, float beta2, float unknown_sigma, int track,
                    uint32_t modes, int64_t* table, int32_t* pred) {
-  if (W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll || (track != kScoreShared && track != kScoreMode) ||
+  if (!window_ok(K, W, M, P) || (track != kScoreShared && track != kScoreMode) ||
       (modes & ~kScoreAllModes))
     return -1;
   return with_team_size(K, [&](auto k) {

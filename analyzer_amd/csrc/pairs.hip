@@ -228,8 +228,7 @@ int64_t pair_tiles(int64_t n) { return (n + kPairTile - 1) / kPairTile; }
 int launch_pair_keys(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
                      const uint32_t* bitmap, uint32_t* ka, uint32_t* kb, uint32_t* bkeep, uint32_t* vals,
                      uint32_t* live_count, hipStream_t s) {
-  if (K < 1 || K > kMaxTeamSize || W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll ||
-      M > kMaxSlots / pair_entries(K) || (modes & ~kPairAllModes))
+  if (!window_ok(K, W, M, P) || M > kMaxSlots / pair_entries(K) || (modes & ~kPairAllModes))
     return (int)hipErrorInvalidValue;
   if (M == 0) return 0;
   if (!aligned(rec, 4) || !aligned(rows, 4) || !aligned(ka, 4) || !aligned(kb, 4) || !aligned(bkeep, 4) ||

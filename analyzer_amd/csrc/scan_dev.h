@@ -2,7 +2,8 @@
 // K17 profiles),
 // device only: the segmented scan by key behind the fold / tile / stitch kernels, and the
 // block sum and block offset behind the count / emit kernels.  docs/ARCHITECTURE.md ("The
-// shared scans") says what they guarantee and how a new feature plugs in.
+// shared scans") says what they guarantee and how a new feature plugs in.  The fold and stitch
+// kernels of K13 and K17 are fold_dev.h on top of the segmented scan.
 #pragma once
 
 #include <hip/hip_runtime.h>

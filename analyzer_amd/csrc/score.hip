@@ -441,8 +441,7 @@ size_t prior_edge_bytes(int64_t n) { return (size_t)(2 * 2 * prior_tiles(n) * kE
 
 int launch_prior_keys(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t* keys,
                       uint32_t* vals, uint32_t* events, uint32_t* slot_priors, hipStream_t s) {
-  if (K < 1 || K > kMaxTeamSize || W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll || M * 2 * K > kMaxSlots)
-    return (int)hipErrorInvalidValue;
+  if (!window_slots_ok(K, W, M, P)) return (int)hipErrorInvalidValue;
   if (M == 0) return 0;
   const unsigned blocks = (unsigned)((M + kPriorThreads - 1) / kPriorThreads);
   with_team_size(K, [&](auto k) {
@@ -455,8 +454,8 @@ int launch_prior_keys(int K, const int32_t* rec, const float* rows, int64_t W, i
 
 int launch_prior_scan(const uint32_t* keys, const uint32_t* vals, const uint32_t* events, int64_t n, int K, int64_t P,
                       float* chain, void* edges, uint32_t* slot_priors, float* priors, hipStream_t s) {
-  if (K < 1 || K > kMaxTeamSize || n < 0 || n > kMaxSlots || n % (2 * K) || P < 0 || P > 0x7fffffffll ||
-      reinterpret_cast<uintptr_t>(slot_priors) % 16 != 0 || reinterpret_cast<uintptr_t>(priors) % 16 != 0)
+  if (!sorted_slots_ok(K, n, P) || reinterpret_cast<uintptr_t>(slot_priors) % 16 != 0 ||
+      reinterpret_cast<uintptr_t>(priors) % 16 != 0)
     return (int)hipErrorInvalidValue;
   if (n == 0) return 0;
   v4u* sp = reinterpret_cast<v4u*>(slot_priors);
@@ -484,7 +483,7 @@ int launch_prior_scan(const uint32_t* keys, const uint32_t* vals, const uint32_t
 int launch_score(int K, const int32_t* rec, const float* priors, const float* rows, int64_t W, int64_t M,
                  const float* attrs, const float* vst, int64_t P, float beta2, float unknown_sigma, int track,
                  uint32_t modes, int64_t* table, int32_t* pred, hipStream_t s) {
-  if (K < 1 || K > kMaxTeamSize || W < 5 * 2 * K + 2 || M < 0 || P < 0 || P > 0x7fffffffll || vst == nullptr ||
+  if (!window_ok(K, W, M, P) || vst == nullptr ||
       table == nullptr || (track != kScoreShared && track != kScoreMode) || (modes & ~kScoreAllModes) ||
       reinterpret_cast<uintptr_t>(attrs) % 16 != 0 || reinterpret_cast<uintptr_t>(priors) % 16 != 0 ||
       reinterpret_cast<uintptr_t>(pred) % 16 != 0)

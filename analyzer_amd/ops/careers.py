@@ -48,6 +48,34 @@ def modes_mask(modes: Optional[Iterable[str]]) -> int:
     return mask
 
 
+def _table_options(noun: str, num_players: int, track: str, score: str) -> int:
+    """The options a per-player table (``noun``: career, profile) is built with, checked; the
+    player count as an int."""
+    if track not in TRACKS:
+        raise ValueError("unknown track %r: one of %s" % (track, ", ".join(TRACKS)))
+    if score not in SCORES:
+        raise ValueError("unknown score %r: one of %s" % (score, ", ".join(SCORES)))
+    num_players = int(num_players)
+    if not 0 <= num_players < 1 << 31:
+        raise ValueError("a %s table holds fewer than 2^31 players" % noun)
+    return num_players
+
+
+def _window_chunks(rec: torch.Tensor, rows: torch.Tensor, K: Optional[int], max_slots: int):
+    """The team size of a window ``rec`` [M, 2K+2] with one row of ``rows`` per record, and
+    the match ranges (a, b) that cut it into chunks of at most ``max_slots`` slots."""
+    if rec.dim() != 2 or rec.shape[1] < 4 or rec.shape[1] % 2:
+        raise ValueError("rec must be [M, 2K+2]")
+    k = (int(rec.shape[1]) - 2) // 2
+    if K is not None and int(K) != k:
+        raise ValueError("rec has team size %d, not %d" % (k, int(K)))
+    M = int(rec.shape[0])
+    if rows.shape[0] != M:
+        raise ValueError("rows must hold one row per record")
+    step = max(1, max_slots // (2 * k))
+    return k, [(a, min(M, a + step)) for a in range(0, M, step)]
+
+
 def _int64(words: torch.Tensor, lo: int) -> torch.Tensor:
     return (words[:, lo].to(torch.int64) & 0xFFFFFFFF) | (words[:, lo + 1].to(torch.int64) << 32)
 
@@ -70,13 +98,7 @@ class CareerTable:
 
     def __init__(self, num_players: int, device, track: str = "shared", score: str = "conservative",
                  modes: Optional[Iterable[str]] = None):
-        if track not in TRACKS:
-            raise ValueError("unknown track %r: one of %s" % (track, ", ".join(TRACKS)))
-        if score not in SCORES:
-            raise ValueError("unknown score %r: one of %s" % (score, ", ".join(SCORES)))
-        self.num_players = int(num_players)
-        if not 0 <= self.num_players < 1 << 31:
-            raise ValueError("a career table holds fewer than 2^31 players")
+        self.num_players = _table_options("career", num_players, track, score)
         self.device = torch.device(device)
         self.track, self.score = track, score
         self.modes = modes_mask(modes)
@@ -91,17 +113,7 @@ class CareerTable:
         ``rows`` [M, W], ``base`` the global index of match 0.  Windows are added in
         chronological order.  A window above the kernels' slot limit is split into
         chunks, which is exact: a career does not depend on how its games are cut."""
-        if rec.dim() != 2 or rec.shape[1] < 4 or rec.shape[1] % 2:
-            raise ValueError("rec must be [M, 2K+2]")
-        k = (int(rec.shape[1]) - 2) // 2
-        if K is not None and int(K) != k:
-            raise ValueError("rec has team size %d, not %d" % (k, int(K)))
-        M = int(rec.shape[0])
-        if rows.shape[0] != M:
-            raise ValueError("rows must hold one row per record")
-        step = max(1, self.max_slots // (2 * k))
-        for a in range(0, M, step):
-            b = min(M, a + step)
+        for a, b in _window_chunks(rec, rows, K, self.max_slots)[1]:
             native().careers_add(self.table, rec[a:b], rows[a:b], int(base) + a, self.num_players,
                                  TRACKS.index(self.track), SCORES.index(self.score), self.modes)
         return self

@@ -35,7 +35,7 @@ import torch
 
 from ..config import MODES
 from ..models.tiers import vst_table
-from .careers import TRACKS, modes_mask
+from .careers import TRACKS, _table_options, _window_chunks, modes_mask
 from .ladder import SCORES
 from .native import native
 from .telemetry import STAT_NAMES
@@ -87,13 +87,7 @@ class ProfileTable:
 
     def __init__(self, num_players: int, device, track: str = "shared", score: str = "conservative",
                  modes: Optional[Iterable[str]] = None, edges: Optional[Sequence[float]] = None):
-        if track not in TRACKS:
-            raise ValueError("unknown track %r: one of %s" % (track, ", ".join(TRACKS)))
-        if score not in SCORES:
-            raise ValueError("unknown score %r: one of %s" % (score, ", ".join(SCORES)))
-        self.num_players = int(num_players)
-        if not 0 <= self.num_players < 1 << 31:
-            raise ValueError("a profile table holds fewer than 2^31 players")
+        self.num_players = _table_options("profile", num_players, track, score)
         self.device = torch.device(device)
         self.track, self.score = track, score
         self.modes = modes_mask(modes)
@@ -114,19 +108,10 @@ class ProfileTable:
         """Fold in one window: its records ``rec`` [M, 2K+2], packed output rows ``rows``
         [M, W] and stat vectors ``stats`` [M, 2K, 8] fp32.  Windows may come in any order.  A
         window above the kernels' slot limit is split into chunks, which is exact."""
-        if rec.dim() != 2 or rec.shape[1] < 4 or rec.shape[1] % 2:
-            raise ValueError("rec must be [M, 2K+2]")
-        k = (int(rec.shape[1]) - 2) // 2
-        if K is not None and int(K) != k:
-            raise ValueError("rec has team size %d, not %d" % (k, int(K)))
-        M = int(rec.shape[0])
-        if rows.shape[0] != M:
-            raise ValueError("rows must hold one row per record")
-        if tuple(stats.shape) != (M, 2 * k, len(STAT_NAMES)):
+        k, chunks = _window_chunks(rec, rows, K, self.max_slots)
+        if tuple(stats.shape) != (int(rec.shape[0]), 2 * k, len(STAT_NAMES)):
             raise ValueError("stats must be [M, 2K, %d]" % len(STAT_NAMES))
-        step = max(1, self.max_slots // (2 * k))
-        for a in range(0, M, step):
-            b = min(M, a + step)
+        for a, b in chunks:
             native().profiles_add(self.table, self.cells, rec[a:b], rows[a:b], stats[a:b], self.num_players,
                                   TRACKS.index(self.track), SCORES.index(self.score), self.modes, self.edges)
         return self

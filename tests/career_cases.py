@@ -206,6 +206,13 @@ def case(name):
         return rec, rows, 9, P, {}
     if kind == "mixed":  # every kind of match, random
         return random_window(3, 900, 50, seed=5, other=0.3) + (0, 50, {})
+    if kind == "nogame":  # the games end inside tile 0: tiles 1 and 2 return early and leave kNoKey edges
+        K, M, P, occupied = 3, 1370, 50, 3000
+        rec, rows = random_window(K, M, P, seed=41, games=occupied, other=0.3)
+        meta0 = rec[:, 2 * K]
+        assert int((((meta0 >> 8) & 0xFF) + ((meta0 >> 16) & 0xFF)).sum()) == occupied  # every game is one of these
+        assert occupied < TILE and 2 * TILE < M * 2 * K
+        return rec, rows, 4, P, {}
     if kind == "real":  # rated by the host mirror; most of the 6000 players never play
         return RC.rated_window(3, 700, 6000) + (1000, 6000, {})
     if kind == "hand":
@@ -225,7 +232,7 @@ def case(name):
 TILE_CASES = ["tile:%d:%d" % (K, n) for K in (1, 2, 3, 4, 5) for n in (TILE - 1, TILE, TILE + 1, 2 * TILE + 3)]
 LONG_CASES = ["alias", "few:2", "few:3"]
 DEVICE_LONG_CASES = LONG_CASES + ["stitch"]  # its expected table is the host mirror's: nothing to check on the CPU
-OTHER_CASES = ["mixed", "real", "hand", "base64", "opt:shared:conservative:ranked", "opt:mode:conservative:",
+OTHER_CASES = ["mixed", "nogame", "real", "hand", "base64", "opt:shared:conservative:ranked", "opt:mode:conservative:",
                "opt:shared:mu:", "opt:mode:mu:casual+blitz", "split"]
 
 

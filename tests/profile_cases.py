@@ -255,6 +255,8 @@ def case(name):
         return with_stats(rec, rows, P, grid, seed=78)
     if kind == "mixed":  # every kind of match, NaN scores among them
         rec, rows = random_window(3, 900, 50, seed=5, other=0.3, nan=0.05)
+        # the games end inside tile 0: tile 1 returns early and leaves kNoKey edges to the stitch
+        assert 0 < int(game_mask(rec, rows, 50)[0].sum()) <= TILE < rec.shape[0] * 6
         return with_stats(rec, rows, 50, grid, seed=6)
     if kind == "onecell":  # one mode, every slot wins, every score in one bracket
         rec, rows = random_window(2, 700, 30, seed=8, modes=1, results=3)
