@@ -17,6 +17,7 @@
 #include "career_core.h"
 #include "common.h"
 #include "gen_core.h"
+#include "hindsight_core.h"
 #include "host.h"
 #include "ingest.h"
 #include "kernels.h"
@@ -1074,6 +1075,56 @@ Tensor priors_add(Tensor chain, Tensor rec, Tensor rows) {
   return priors;
 }
 
+// K16 (hindsight.hip; host mirror host.cpp host_hindsight_add): [out, bad] of one window -- out
+// [M, 2K, 2] fp32, the smoothed (mu, sigma) of every element and NaN elsewhere; bad int64 [1], the
+// slots skipped for their values -- against the carry table [P, 2] fp64, advanced in place to
+// every player's oldest element (hindsight_core.h).  Windows come newest first.  The device path
+// is five stream-ordered steps (keys, sort, summaries, stitch, apply) without a host read.
+std::vector<Tensor> hindsight_add(Tensor carry, Tensor rec, Tensor rows, double tau, int64_t track, int64_t mode) {
+  const auto dev = carry.device();
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "hindsight_add: rec must be [M, 2K+2]");
+  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t M = check_window(rec, rows, K, dev, "hindsight_add");
+  check_slots(M, K, "hindsight_add");
+  TORCH_CHECK(carry.dim() == 2, "hindsight_add: carry must be [P, 2]");
+  const int64_t P = carry.size(0);
+  TORCH_CHECK(P <= 0x7fffffffLL, "hindsight_add: P must fit in int32");
+  check_rows(carry, "carry", P, 2, dev, torch::kFloat64);
+  TORCH_CHECK(std::isfinite(tau) && tau >= 0.0, "hindsight_add: tau must be finite and >= 0, got ", tau);
+  TORCH_CHECK(track == ana::kHsShared || track == ana::kHsMode, "hindsight_add: unknown track ", track);
+  TORCH_CHECK(track != ana::kHsMode || (mode >= 0 && mode < ana::kModes), "hindsight_add: a mode track needs a mode "
+              "0..5, got ", mode);
+  const double tau2 = tau * tau;
+  Tensor out = torch::empty({M, 2 * K, 2}, rows.options());
+  if (!dev.is_cuda()) {
+    Tensor bad = torch::zeros({1}, torch::TensorOptions().dtype(torch::kInt64));
+    TORCH_CHECK(ana::host_hindsight_add((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                        tau2, (int)track, (int)mode, carry.data_ptr<double>(), out.data_ptr<float>(),
+                                        bad.data_ptr<int64_t>()) == 0,
+                "hindsight_add: bad arguments");
+    return {out, bad};
+  }
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
+  Tensor bad = torch::zeros({1}, i32);
+  if (M == 0) return {out, bad.to(torch::kInt64)};
+  const hipStream_t s = stream_of(carry);
+  const int64_t n = M * 2 * K;
+  Tensor keys = torch::empty({n}, i32), vals = torch::empty({n}, i32);
+  Tensor events = torch::empty({n, 2}, i32);
+  check_hip(ana::launch_hindsight_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                       (int)track, (int)mode, u32p(keys), u32p(vals), u32p(events),
+                                       out.data_ptr<float>(), bad.data_ptr<int32_t>(), s),
+            "hindsight_keys");
+  if (P > 0) {
+    const auto sorted = sort_pairs_on_stream(keys, vals, n, bit_length(P), s);
+    Tensor edges = torch::empty({(int64_t)ana::hindsight_edge_bytes(n)}, i32.dtype(torch::kUInt8));
+    check_hip(ana::launch_hindsight_scan(u32p(sorted[0]), u32p(sorted[1]), u32p(events), n, (int)K, P, tau2,
+                                         carry.data_ptr<double>(), edges.data_ptr<uint8_t>(), out.data_ptr<float>(), s),
+              "hindsight_scan");
+  }
+  return {out, bad.to(torch::kInt64)};
+}
+
 // adds the predictions of one window's priors to the scorecard table [6, 33, 4] int64 in
 // place; returns the pred rows [M, 4] int32 (flags word, p_win0 bits, p_outcome bits, 0) when
 // ``keep``, else an empty tensor
@@ -1543,6 +1594,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("PROFILE_TILE") = ana::kProfileTile;
   m.def("priors_add", &priors_add, "K14: the pre-match priors [M, 4 * 2K] fp32 of one window (rec [M, 2K+2] joined with "
         "its packed rows [M, W]) against the chain table [P, 16], advanced in place: priors_add(chain, rec, rows)");
+  m.def("hindsight_add", &hindsight_add, "K16: [out [M, 2K, 2] fp32, bad int64 [1]] -- the smoothed (mu, sigma) of one "
+        "window (rec [M, 2K+2] joined with its packed rows [M, W]; windows newest first) against the carry table "
+        "[P, 2] fp64, advanced in place: hindsight_add(carry, rec, rows, tau, track, mode)",
+        py::arg("carry"), py::arg("rec"), py::arg("rows"), py::arg("tau"), py::arg("track"), py::arg("mode"));
+  m.attr("HINDSIGHT_TILE") = ana::kHindsightTile;
+  m.attr("HINDSIGHT_BUDGET_C") = ana::kHsBudgetC;
   m.def("score_add", &score_add, "K14: add the predictions of a window's priors to the scorecard table [6, 33, 4] int64 "
         "in place; returns the pred rows [M, 4] int32 when keep: score_add(table, rec, priors, rows, attrs, vst, P, "
         "beta2, unknown_sigma, track, modes, keep)",

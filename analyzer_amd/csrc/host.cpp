@@ -14,6 +14,7 @@
 
 #include "career_core.h"
 #include "gen_core.h"
+#include "hindsight_core.h"
 #include "ladder_core.h"
 #include "matchmake_core.h"
 #include "pair_core.h"
@@ -619,6 +620,56 @@ int host_priors_add(int K, const int32_t* rec, const float* rows, int64_t W, int
   if (!window_ok(K, W, M, P)) return -1;
   return with_team_size(K, [&](auto k) { priors_add_k<decltype(k)::value>(rec, rows, W, M, P, chain, priors); })
              ? 0 : -1;
+}
+
+// K16: the smoother's recursion, newest match first; the carry row of a player is the
+// smoothed state of the element after the one at hand
+template <int K>
+static void hindsight_add_k(const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, double tau2,
+                            int track, int mode, double* carry, float* out, int64_t* bad) {
+  constexpr int S = 2 * K;
+  for (int64_t m = M - 1; m >= 0; --m) {
+    const int32_t* r = rec + m * (S + 2);
+    float* o = out + m * (2 * S);
+    for (int j = 0; j < 2 * S; ++j) o[j] = NAN;
+    const uint32_t live = prior_live_mask<K>(r, P);
+    if (!live) continue;  // the row is only read for a live slot
+    uint32_t row[5 * S + 2];
+    memcpy(row, rows + m * W, sizeof(row));
+    const uint32_t elems = hs_element_mask<K>(r, live, select_row_status<K>(row), track, mode);
+    const uint32_t* mu = row + (track == kHsMode ? 3 * S : 0);
+    for (int j = 0; j < S; ++j) {
+      if (!((elems >> j) & 1u)) continue;
+      float m_t, s_t;
+      memcpy(&m_t, mu + j, 4);
+      memcpy(&s_t, mu + S + j, 4);
+      if (!hs_value_ok(m_t, s_t)) {
+        ++*bad;
+        continue;
+      }
+      double* c = carry + (int64_t)r[j] * 2;
+      double mh = (double)m_t, ph = (double)s_t * (double)s_t;
+      if (c[0] == c[0]) {
+        const double p_t = ph, g = hs_gain(p_t, tau2);
+        mh = (double)m_t + g * (c[0] - (double)m_t);
+        ph = p_t + (g * g) * (c[1] - p_t - tau2);
+      }
+      c[0] = mh;
+      c[1] = ph;
+      o[2 * j] = (float)mh;
+      o[2 * j + 1] = (float)sqrt(ph);
+    }
+  }
+}
+
+int host_hindsight_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, double tau2,
+                       int track, int mode, double* carry, float* out, int64_t* bad) {
+  if (!window_ok(K, W, M, P) || !(tau2 >= 0.0) || !std::isfinite(tau2) || (track != kHsShared && track != kHsMode) ||
+      (track == kHsMode && (mode < 0 || mode >= kModes)))
+    return -1;
+  return with_team_size(K, [&](auto k) {
+    hindsight_add_k<decltype(k)::value>(rec, rows, W, M, P, tau2, track, mode, carry, out, bad);
+  }) ? 0 : -1;
 }
 
 // K14: the prediction of every match from its priors, on preview's fp64 path, and its score

@@ -86,6 +86,12 @@ using PairMap = std::map<int64_t, std::array<int32_t, 4>>;
 int host_pairs_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
                    const uint32_t* bitmap, PairMap& table);
 void host_pairs_merge(const int64_t* keys, const int32_t* counts, int64_t n, PairMap& table);
+// K16 host mirror (hindsight_core.h): the recursion itself, walked backwards over rec [M][2K+2]
+// joined with rows [M][W] in fp64 -- not the composition of maps the device scans -- against
+// carry [P][2] (mh, Ph; NaN: no later match), which is left at every player's oldest element.
+// out [M][2K][2] fp32 (NaN where no element); *bad is incremented.  -1: bad arguments.
+int host_hindsight_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, double tau2,
+                       int track, int mode, double* carry, float* out, int64_t* bad);
 // K17 host mirror (profile_core.h): the games of rec [M][2K+2] joined with rows [M][W] and stats
 // [M][2K][8], each added to its row of table [P][kProfileWords] and its cell of cells
 // [profile_table_words(n_edges + 1)], bit-identical to the device.  -1: bad arguments.

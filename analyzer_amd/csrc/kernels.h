@@ -164,6 +164,25 @@ int launch_pair_emit(const uint32_t* a, const uint32_t* b, const uint32_t* vals,
                      const int32_t* src, const int64_t* offsets, int64_t U, int64_t* keys, int32_t* counts,
                      hipStream_t s);
 
+// K16 hindsight (hindsight.hip, hindsight_core.h): the smoothed (mu, sigma) of one window rec
+// [M][2K+2] joined with its packed rows [M][W] (alignment as for K10), M * 2K <= kMaxSlots;
+// windows come newest first.  track: HsTrack; mode: the mode 0..5 of a kHsMode track.
+// hindsight_keys writes per slot i = m * 2K + j, at the mirrored position n - 1 - i, the sort key
+// (the player of an element, else P) and the value i, at events[i] (2 words per slot, 8-B
+// aligned) the (mu, sigma) bits of an element and at out[i] (out [M][2K][2] fp32, 8-B aligned)
+// the (NaN, NaN) of a slot that is none, and adds the bad slots to *bad; the pairs are sorted with
+// launch_radix_sort_pairs on bit_length(P) bits; hindsight_scan takes the sorted pairs [n = M *
+// 2K], stores the smoothed pair of every element in out and advances carry [P][2] fp64 (mh, Ph;
+// NaN: no later match) in place (tau2 finite and >= 0; edges: hindsight_edge_bytes(n) bytes, 8-B
+// aligned).  Everything is stream-ordered.
+constexpr int kHindsightTile = 4096;  // sorted elements per workgroup of the scan
+size_t hindsight_edge_bytes(int64_t n);
+int launch_hindsight_keys(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, int track,
+                          int mode, uint32_t* keys, uint32_t* vals, uint32_t* events, float* out, int32_t* bad,
+                          hipStream_t s);
+int launch_hindsight_scan(const uint32_t* keys, const uint32_t* vals, const uint32_t* events, int64_t n, int K,
+                          int64_t P, double tau2, double* carry, void* edges, float* out, hipStream_t s);
+
 // K17 profiles (profile.hip, profile_core.h): one window rec [M][2K+2] joined with its packed rows
 // [M][W] (alignment as for K10) and its stat vectors stats [M][2K][8] fp32 (16-B aligned), M * 2K
 // <= kMaxSlots.  profile_keys writes per slot i = m * 2K + j the sort key (the player of a game,

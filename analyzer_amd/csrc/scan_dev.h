@@ -1,5 +1,5 @@
 // Workgroup scans of the analytics kernels (K10 select, K13 careers, K14 scorecard, K15 pairs,
-// K17 profiles),
+// K16 hindsight, K17 profiles),
 // device only: the segmented scan by key behind the fold / tile / stitch kernels, and the
 // block sum and block offset behind the count / emit kernels.  docs/ARCHITECTURE.md ("The
 // shared scans") says what they guarantee and how a new feature plugs in.  The fold and stitch

@@ -7,3 +7,4 @@ from .pairs import PairTable  # noqa: F401
 from .profiles import ProfileTable  # noqa: F401
 from .matchmake import (Balanced, Preview, balance_lobbies, fill_winners, make_lobbies,  # noqa: F401
                         preview_matches)
+from .hindsight import Hindsight  # noqa: F401

@@ -31,6 +31,9 @@ for K = 4, 5).  ``records="resident"`` keeps them where the executor writes them
   ``Scorecard``, csrc/score.hip, K14): the belief before every match is reconstructed from
   the rows and the roster the history started from, and the win probability it gives is
   scored against the outcome.  One rank only.
+* ``hindsight(num_players, rec_of, players)`` smooths every player's skill curve backwards
+  over the filled windows (``ops/hindsight.py`` ``Hindsight``, csrc/hindsight.hip, K16) and
+  returns the filtered and the smoothed curve of the listed players.  One rank only.
 * ``export`` / ``load`` move the filled rows through two pinned slots on a copy stream
   into one flat file plus a small JSON header; the round trip is bit-identical.  This
   is how an arena is persisted: checkpoints do not hold arena rows, so a resumed run
@@ -48,6 +51,7 @@ from typing import Callable, Dict, Iterator, Optional, Sequence, Tuple, Union
 import torch
 
 from ..ops.careers import CareerTable
+from ..ops.hindsight import SHARED, Hindsight
 from ..ops.native import native
 from ..ops.pairs import PairTable
 from ..ops.rate import RateResult, Roster
@@ -252,6 +256,39 @@ class RecordArena:
             a = int(self.local_row(lo))
             card.add(rec_of(lo, hi), self.rows[a:a + hi - lo])
         return card
+
+    def hindsight(self, num_players: int, rec_of: Callable[[int, int], torch.Tensor], players: Sequence[int],
+                  **kw) -> Dict[str, torch.Tensor]:
+        """The filtered and the smoothed skill curve (``ops/hindsight.py``, K16) of ``players``
+        over the filled windows, which are walked newest first; ``kw``: ``track``, ``cfg`` of
+        ``Hindsight``.  Columnar tensors in chronological order, one entry per rated match of a
+        listed player on the track: ``match`` (int64 global index), ``player``, ``slot``,
+        ``mu``, ``sigma`` (filtered), ``mu_s``, ``sigma_s`` (smoothed).  A chain needs the whole
+        history, so on N > 1 ranks this raises."""
+        if self.size > 1:
+            raise ValueError("hindsight chains the whole history: it needs a one-rank arena, this is rank %d of %d"
+                             % (self.rank, self.size))
+        hs = Hindsight(num_players, self.device, **kw)
+        mu_name, sigma_name = ("s_mu", "s_sig") if hs.track == SHARED else ("m_mu", "m_sig")
+        bitmap = player_bitmap(players, num_players, self.device)
+        names = ("match", "player", "slot", "mu", "sigma", "mu_s", "sigma_s")
+        parts = []
+        for lo, hi in reversed(list(self.windows())):
+            rec = rec_of(lo, hi)
+            a = int(self.local_row(lo))
+            rows = self.rows[a:a + hi - lo]
+            smooth = hs.add(rec, rows, K=self.K).reshape(-1, 2)
+            cols = hits_columns(records_select(rec, rows, lo, num_players, bitmap))
+            at = (cols["match"] - lo) * (2 * self.K) + cols["slot"].to(torch.int64)
+            pair = smooth.index_select(0, at)
+            keep = ~torch.isnan(pair[:, 1])  # the hits that are elements of the track
+            parts.append((cols["match"][keep], cols["player"][keep], cols["slot"][keep], cols[mu_name][keep],
+                          cols[sigma_name][keep], pair[keep, 0], pair[keep, 1]))
+        parts.reverse()
+        if not parts:
+            dt = (torch.int64, torch.int32, torch.int32) + (torch.float32,) * 4
+            return {n: torch.empty(0, dtype=d, device=self.device) for n, d in zip(names, dt)}
+        return {n: torch.cat([p[i] for p in parts]) for i, n in enumerate(names)}
 
     # ------------------------------------------------------------ sizing
     @staticmethod

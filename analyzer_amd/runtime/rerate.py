@@ -46,6 +46,8 @@ streams a long synthetic history through the engine window by window:
         --window 16000000 --records resident --score mode     # the scorecard of the run (ops/scorecard.py)
     python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
         --window 16000000 --records resident --pairs 17,4242  # whom they play with and against (ops/pairs.py)
+    python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
+        --window 16000000 --records resident --hindsight 17,4242 --hindsight-track ranked  # smoothed curves (ops/hindsight.py)
 """
 from __future__ import annotations
 
@@ -62,6 +64,7 @@ import torch
 
 from ..config import EngineConfig, RaterConfig
 from ..ops import rate as R
+from ..ops.hindsight import track_of
 from ..ops.ladder import build_ladder, track_index
 from ..ops.matchmake import make_lobbies, mode_index, preview_matches, queue_order
 from ..ops.synth import RosterSpec, StreamSpec, make_roster, make_stream
@@ -430,6 +433,19 @@ def career_lines(table, ids) -> list:
                  **{name: _num(vals[i]) for name, vals in cols.items()}) for i, p in enumerate(ids)]
 
 
+def hindsight_lines(curves: dict, ids, track: str) -> list:
+    """One JSON-ready dict per player of ``ids`` from a ``RecordArena.hindsight`` result: the
+    matches of the player's chain with the filtered and the smoothed (mu, sigma) at each."""
+    lines = []
+    for p in ids:
+        sel = (curves["player"] == p).nonzero().reshape(-1)
+        line = {"hindsight": int(p), "track": track, "records": int(sel.numel())}
+        for name in ("match", "mu", "sigma", "mu_s", "sigma_s"):
+            line[name] = [_num(v) for v in curves[name].index_select(0, sel).cpu().tolist()]
+        lines.append(line)
+    return lines
+
+
 def pair_lines(table, ids, top: int = 5) -> list:
     """One JSON-ready dict per player of ``ids`` from a ``PairTable`` (ops/pairs.py): the number
     of distinct players it shared a rated match with, and its ``top`` most frequent team mates
@@ -522,6 +538,12 @@ def main(argv=None) -> int:
                     help="with --careers: score the shared track or each match's mode track")
     ap.add_argument("--careers-modes", default=None, metavar="MODE[,MODE...]",
                     help="with --careers: count only the matches of these modes (default: all)")
+    ap.add_argument("--hindsight", default=None, metavar="ID[,ID...]",
+                    help="with --records resident: print each player's filtered and smoothed skill curve after the "
+                         "run (JSON lines; one rank only): the curve smoothed backwards over the player's own rated "
+                         "matches, not a re-run of the match factors")
+    ap.add_argument("--hindsight-track", default=None, metavar="TRACK",
+                    help="with --hindsight: the shared track (default) or a mode's")
     ap.add_argument("--pairs", default=None, metavar="ID[,ID...]",
                     help="with --records resident: print whom each player played with and against after the run "
                          "(JSON lines): the distinct partners and the most frequent team mates and opponents")
@@ -569,6 +591,20 @@ def main(argv=None) -> int:
         ap.error("--careers: %s" % e)
     if any(p < 0 or p >= spec.players for p in career_ids):
         ap.error("--careers ids must lie in [0, %d)" % spec.players)
+    if args.hindsight and not resident:
+        ap.error("--hindsight needs --records resident")
+    if args.hindsight_track and not args.hindsight:
+        ap.error("--hindsight-track needs --hindsight")
+    if args.hindsight and size > 1:
+        ap.error("--hindsight chains the whole history: it runs on one rank")
+    hindsight_track = args.hindsight_track or "shared"
+    try:
+        hindsight_ids = [int(p) for p in (args.hindsight or "").split(",") if p.strip()]
+        track_of(hindsight_track)
+    except ValueError as e:
+        ap.error("--hindsight: %s" % e)
+    if any(p < 0 or p >= spec.players for p in hindsight_ids):
+        ap.error("--hindsight ids must lie in [0, %d)" % spec.players)
     if args.pairs and not resident:
         ap.error("--pairs needs --records resident")
     if (args.pairs_modes or args.pairs_top is not None) and not args.pairs:
@@ -675,6 +711,11 @@ def main(argv=None) -> int:
                             players=pair_ids)  # this rank's blocks
         for line in pair_lines(table, pair_ids, pair_top):
             print(json.dumps(dict(line, rank=rank)), flush=True)
+    if hindsight_ids:
+        curves = arena.hindsight(spec.players, stream_records(spec, arena.device), hindsight_ids,
+                                 track=hindsight_track)
+        for line in hindsight_lines(curves, hindsight_ids, hindsight_track):
+            print(json.dumps(line), flush=True)
     if args.score:
         card = arena.scorecard(roster0, stream_records(spec, arena.device), track=args.score, modes=score_modes)
         print(json.dumps({"scorecard": card.summary()}), flush=True)
