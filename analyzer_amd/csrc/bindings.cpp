@@ -20,6 +20,7 @@
 #include "hindsight_core.h"
 #include "host.h"
 #include "ingest.h"
+#include "island_core.h"
 #include "kernels.h"
 #include "ladder_core.h"
 #include "matchmake_core.h"
@@ -1035,6 +1036,106 @@ void profiles_add(Tensor table, Tensor cells, Tensor rec, Tensor rows, Tensor st
             "profile_fold");
 }
 
+// K18 (islands.hip; host mirror host.cpp host_islands_*; island_core.h): the state of an island
+// forest -- parent, slots, credit int32 [P] and ctrl int64 [2] on one device -> that device
+torch::Device check_island_state(const Tensor& parent, const Tensor* slots, const Tensor* credit, const Tensor* ctrl,
+                                 int64_t P, const char* what) {
+  const auto dev = parent.device();
+  TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, what, ": P must fit in int32");
+  check(parent, "parent", torch::kInt32, dev);
+  TORCH_CHECK(parent.dim() == 1 && parent.numel() == P, what, ": parent must be [P]");
+  if (slots != nullptr) {
+    check(*slots, "slots", torch::kInt32, dev);
+    TORCH_CHECK(slots->dim() == 1 && slots->numel() == P, what, ": slots must be [P]");
+  }
+  if (credit != nullptr) {
+    check(*credit, "credit", torch::kInt32, dev);
+    TORCH_CHECK(credit->dim() == 1 && credit->numel() == P, what, ": credit must be [P]");
+  }
+  if (ctrl != nullptr) {
+    check(*ctrl, "ctrl", torch::kInt64, dev);
+    TORCH_CHECK(ctrl->numel() == ana::kIslandCtrlWords, what, ": ctrl must hold ", ana::kIslandCtrlWords, " words");
+  }
+  return dev;
+}
+
+// unites the live slots of every rated match of one window -- rec [M, 2K+2] joined with its
+// packed output rows [M, W] -- and counts them, in place
+void islands_add(Tensor parent, Tensor slots, Tensor credit, Tensor ctrl, Tensor rec, Tensor rows, int64_t P,
+                 int64_t modes) {
+  const auto dev = check_island_state(parent, &slots, &credit, &ctrl, P, "islands_add");
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "islands_add: rec must be [M, 2K+2]");
+  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t M = check_window(rec, rows, K, dev, "islands_add");
+  check_slots(M, K, "islands_add");
+  TORCH_CHECK(modes >= 0 && (modes & ~(int64_t)ana::kIslandAllModes) == 0,
+              "islands_add: the modes mask must name modes 0..5");
+  if (M == 0 || P == 0) return;
+  if (!dev.is_cuda()) {
+    TORCH_CHECK(ana::host_islands_add((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                      (uint32_t)modes, parent.data_ptr<int32_t>(), slots.data_ptr<int32_t>(),
+                                      credit.data_ptr<int32_t>()) == 0,
+                "islands_add: bad arguments or a parent word outside [0, its index]");
+    return;
+  }
+  check_hip(ana::launch_island_hook((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                    (uint32_t)modes, parent.data_ptr<int32_t>(), slots.data_ptr<int32_t>(),
+                                    credit.data_ptr<int32_t>(), ctrl.data_ptr<int64_t>(), stream_of(parent)),
+            "island_hook");
+}
+
+// the same unions for the edges (a[i], b[i]); mark: the endpoints become seen
+void islands_edges(Tensor parent, Tensor slots, Tensor ctrl, Tensor a, Tensor b, int64_t P, bool mark) {
+  const auto dev = check_island_state(parent, &slots, nullptr, &ctrl, P, "islands_edges");
+  check(a, "a", torch::kInt32, dev);
+  check(b, "b", torch::kInt32, dev);
+  TORCH_CHECK(a.dim() == 1 && b.dim() == 1 && a.numel() == b.numel(), "islands_edges: a and b must be [n]");
+  const int64_t n = a.numel();
+  if (n == 0) return;
+  if (!dev.is_cuda()) {
+    TORCH_CHECK(ana::host_islands_edges(a.data_ptr<int32_t>(), b.data_ptr<int32_t>(), n, P, mark ? 1 : 0,
+                                        parent.data_ptr<int32_t>(), slots.data_ptr<int32_t>(),
+                                        ctrl.data_ptr<int64_t>()) == 0,
+                "islands_edges: bad arguments or a parent word outside [0, its index]");
+    return;
+  }
+  check_hip(ana::launch_island_edges(a.data_ptr<int32_t>(), b.data_ptr<int32_t>(), n, P, mark ? 1 : 0,
+                                     parent.data_ptr<int32_t>(), slots.data_ptr<int32_t>(), ctrl.data_ptr<int64_t>(),
+                                     stream_of(parent)),
+            "island_edges");
+}
+
+// parent[i] = the smallest id of i's island
+void islands_flatten(Tensor parent, Tensor ctrl, int64_t P) {
+  const auto dev = check_island_state(parent, nullptr, nullptr, &ctrl, P, "islands_flatten");
+  if (P == 0) return;
+  if (!dev.is_cuda()) {
+    TORCH_CHECK(ana::host_islands_flatten(parent.data_ptr<int32_t>(), P) == 0,
+                "islands_flatten: a parent word outside [0, its index]");
+    return;
+  }
+  check_hip(ana::launch_island_flatten(parent.data_ptr<int32_t>(), P, ctrl.data_ptr<int64_t>(), stream_of(parent)),
+            "island_flatten");
+}
+
+// census [3, P] int64 of flattened parents: players, matches, player_games at each root's index
+Tensor islands_census(Tensor parent, Tensor slots, Tensor credit, Tensor ctrl, int64_t P) {
+  const auto dev = check_island_state(parent, &slots, &credit, &ctrl, P, "islands_census");
+  Tensor census = torch::zeros({(int64_t)ana::kIslandCensusRows, P}, parent.options().dtype(torch::kInt64));
+  if (P == 0) return census;
+  if (!dev.is_cuda()) {
+    TORCH_CHECK(ana::host_islands_census(parent.data_ptr<int32_t>(), slots.data_ptr<int32_t>(),
+                                         credit.data_ptr<int32_t>(), P, census.data_ptr<int64_t>()) == 0,
+                "islands_census: a parent word outside [0, its index]");
+    return census;
+  }
+  check_hip(ana::launch_island_census(parent.data_ptr<int32_t>(), slots.data_ptr<int32_t>(),
+                                      credit.data_ptr<int32_t>(), P, census.data_ptr<int64_t>(),
+                                      ctrl.data_ptr<int64_t>(), stream_of(parent)),
+            "island_census");
+  return census;
+}
+
 // priors [M, 4 * 2K] fp32 (field-major: shared mu, sigma, mode mu, sigma) of one window against
 // the chain table [P, 16] (mu, sigma per granule), which is advanced in place to the state
 // after the window (score_core.h).  The device path is six stream-ordered steps (keys, sort,
@@ -1617,6 +1718,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     TORCH_CHECK(K >= 1 && K <= ana::kMaxTeamSize, "PAIR_ENTRIES: K must be 1..5");
     return (int64_t)ana::pair_entries((int)K);
   }, "K15: entries of a match of team size K, 2K(2K - 1)");
+  m.def("islands_add", &islands_add, "K18: unite the live slots of every rated match of one window (rec [M, 2K+2] joined "
+        "with its packed rows [M, W]) in the island forest, in place: islands_add(parent, slots, credit, ctrl, rec, rows, "
+        "P, modes)");
+  m.def("islands_edges", &islands_edges, "K18: the same unions for the edges (a[i], b[i]); bad edges are counted in ctrl[1]: "
+        "islands_edges(parent, slots, ctrl, a, b, P, mark)");
+  m.def("islands_flatten", &islands_flatten, "K18: parent[i] = the smallest id of i's island: islands_flatten(parent, ctrl, P)");
+  m.def("islands_census", &islands_census, "K18: [3, P] int64 (players, matches, player_games at each root) of flattened "
+        "parents: islands_census(parent, slots, credit, ctrl, P)");
+  m.attr("ISLAND_SEEN_BIT") = (int64_t)ana::kIslandSeenBit;
+  m.attr("ISLAND_ERR_STEPS") = (int64_t)ana::kIslandErrSteps;
+  m.attr("ISLAND_ERR_PARENT") = (int64_t)ana::kIslandErrParent;
   m.attr("SCORE_BINS") = ana::kScoreBins;
   m.attr("PRIOR_TILE") = ana::kPriorTile;
   m.attr("NLOG2_CAP") = (int64_t)ana::kNlog2Cap;

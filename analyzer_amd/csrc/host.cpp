@@ -15,6 +15,7 @@
 #include "career_core.h"
 #include "gen_core.h"
 #include "hindsight_core.h"
+#include "island_core.h"
 #include "ladder_core.h"
 #include "matchmake_core.h"
 #include "pair_core.h"
@@ -475,6 +476,106 @@ void host_pairs_merge(const int64_t* keys, const int32_t* counts, int64_t n, Pai
     auto& row = table[keys[i]];
     for (int d = 0; d < kPairWords; ++d) row[d] += counts[i * kPairWords + d];
   }
+}
+
+// K18: the sequential union-find.  -1 from find: a word outside [0, its index]
+static int32_t island_find_host(int32_t* parent, int32_t x) {
+  for (;;) {
+    const int32_t p = parent[x];
+    if (p == x) return x;
+    if (!island_word_ok(p, x)) return -1;
+    const int32_t g = parent[p];
+    if (!island_word_ok(g, p)) return -1;
+    parent[x] = g;  // path halving
+    x = g;
+  }
+}
+
+static bool island_unite_host(int32_t* parent, int32_t a, int32_t b) {
+  a = island_find_host(parent, a);
+  b = island_find_host(parent, b);
+  if (a < 0 || b < 0) return false;
+  if (a != b) parent[a > b ? a : b] = a > b ? b : a;
+  return true;
+}
+
+template <int K>
+static bool islands_add_k(const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
+                          int32_t* parent, int32_t* slots, int32_t* credit) {
+  constexpr int S = 2 * K;
+  for (int64_t m = 0; m < M; ++m) {
+    const int32_t* r = rec + m * (S + 2);
+    const uint32_t live = island_live_mask<K>(r, P, modes);
+    if (live == 0u) continue;
+    uint32_t st;
+    memcpy(&st, rows + m * W + 5 * S + 1, sizeof(st));
+    if ((st & 0xffu) != kRated) continue;
+    int32_t first = -1;
+    for (int j = 0; j < S; ++j) {
+      if (!((live >> j) & 1u)) continue;
+      const int32_t p = r[j];
+      slots[p] += 1;
+      if (first < 0) {
+        first = p;
+        credit[p] += 1;
+      } else if (p != first && !island_unite_host(parent, first, p)) {
+        return false;
+      }
+    }
+  }
+  return true;
+}
+
+int host_islands_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
+                     int32_t* parent, int32_t* slots, int32_t* credit) {
+  if (!window_ok(K, W, M, P) || (modes & ~kIslandAllModes)) return -1;
+  bool ok = true;
+  const bool known = with_team_size(K, [&](auto k) {
+    ok = islands_add_k<decltype(k)::value>(rec, rows, W, M, P, modes, parent, slots, credit);
+  });
+  return known && ok ? 0 : -1;
+}
+
+int host_islands_edges(const int32_t* a, const int32_t* b, int64_t n, int64_t P, int mark, int32_t* parent,
+                       int32_t* slots, int64_t* ctrl) {
+  if (n < 0 || P < 0 || P > 0x7fffffffll) return -1;
+  for (int64_t i = 0; i < n; ++i) {
+    if (a[i] < 0 || (int64_t)a[i] >= P || b[i] < 0 || (int64_t)b[i] >= P) {
+      ctrl[1] += 1;
+      continue;
+    }
+    if (mark) {
+      slots[a[i]] = (int32_t)((uint32_t)slots[a[i]] | kIslandSeenBit);
+      slots[b[i]] = (int32_t)((uint32_t)slots[b[i]] | kIslandSeenBit);
+    }
+    if (a[i] != b[i] && !island_unite_host(parent, a[i], b[i])) return -1;
+  }
+  return 0;
+}
+
+int host_islands_flatten(int32_t* parent, int64_t P) {
+  if (P < 0 || P > 0x7fffffffll) return -1;
+  for (int64_t i = 0; i < P; ++i) {  // ascending: parent[i] <= i is flat already when i is reached
+    const int32_t p = parent[i];
+    if (!island_word_ok(p, (int32_t)i)) return -1;
+    parent[i] = parent[p];
+  }
+  return 0;
+}
+
+int host_islands_census(const int32_t* parent, const int32_t* slots, const int32_t* credit, int64_t P,
+                        int64_t* census) {
+  if (P < 0 || P > 0x7fffffffll) return -1;
+  for (int64_t i = 0; i < P; ++i) {
+    const uint32_t sw = (uint32_t)slots[i];
+    if (sw == 0u) continue;
+    const int32_t root = parent[i];
+    if (!island_word_ok(root, (int32_t)i)) return -1;
+    census[root] += 1;
+    census[P + root] += credit[i];
+    census[2 * P + root] += (int64_t)(sw & kIslandSlotMask);
+  }
+  return 0;
 }
 
 // K11: the device's three stages on one track -- keys in id order, a stable sort of the

@@ -98,6 +98,18 @@ int host_hindsight_add(int K, const int32_t* rec, const float* rows, int64_t W, 
 int host_profiles_add(int K, const int32_t* rec, const float* rows, int64_t W, const float* stats, int64_t M,
                       int64_t P, int track, int score, uint32_t modes, const float* edges, int n_edges,
                       int32_t* table, int64_t* cells);
+// K18 host mirror (island_core.h): the plain sequential union-find -- find with path halving,
+// the larger root hooked under the smaller -- over parent / slots / credit [P] and ctrl
+// [kIslandCtrlWords], with the device's liveness rules and counters.  After host_islands_flatten
+// parent is the device's, bit for bit; census [kIslandCensusRows][P] is added to.  -1: bad
+// arguments, or a parent word outside [0, its index].
+int host_islands_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
+                     int32_t* parent, int32_t* slots, int32_t* credit);
+int host_islands_edges(const int32_t* a, const int32_t* b, int64_t n, int64_t P, int mark, int32_t* parent,
+                       int32_t* slots, int64_t* ctrl);
+int host_islands_flatten(int32_t* parent, int64_t P);
+int host_islands_census(const int32_t* parent, const int32_t* slots, const int32_t* credit, int64_t P,
+                        int64_t* census);
 // K12 host mirror (matchmake_core.h); out / records as launch_preview / launch_balance /
 // launch_queue_keys (kernels.h) lay them out; attrs may be null.  preview runs rate's own
 // fp64 path (status and quality are the bits host_rate writes); balance chooses the split in

@@ -201,6 +201,23 @@ int launch_profile_keys(int K, const int32_t* rec, const float* rows, int64_t W,
 int launch_profile_fold(const uint32_t* keys, const uint32_t* vals, const float* stats, int64_t n, int K, int64_t P,
                         int32_t* table, void* edges, hipStream_t s);
 
+// K18 islands (islands.hip, island_core.h): the connected components of the match graph as a
+// union-find over parent / slots / credit int32 [P], updated in place; ctrl: kIslandCtrlWords
+// int64 ([0] sticky error bits, [1] edges dropped as bad).  island_hook takes one window rec
+// [M][2K+2] joined with its packed rows [M][W] (alignment as for K10), M * 2K <= kMaxSlots;
+// island_edges the edges (a[i], b[i]), i < n, and marks their endpoints seen when mark != 0;
+// island_flatten, a launch after the last of those, leaves parent[i] = the smallest id of i's
+// island; island_census then adds the seen players of flattened parents to census
+// [kIslandCensusRows][P] int64 (zeroed by the caller): players, matches, player_games at the
+// root's index.  Everything is stream-ordered; no lane waits for another.
+int launch_island_hook(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t modes,
+                       int32_t* parent, int32_t* slots, int32_t* credit, int64_t* ctrl, hipStream_t s);
+int launch_island_edges(const int32_t* a, const int32_t* b, int64_t n, int64_t P, int mark, int32_t* parent,
+                        int32_t* slots, int64_t* ctrl, hipStream_t s);
+int launch_island_flatten(int32_t* parent, int64_t P, int64_t* ctrl, hipStream_t s);
+int launch_island_census(const int32_t* parent, const int32_t* slots, const int32_t* credit, int64_t P,
+                         int64_t* census, int64_t* ctrl, hipStream_t s);
+
 // Stable LSD radix sort of (key, value) pairs on the low ``bits`` key bits
 // (radix_sort.hip).  Ping-pongs between the two buffer pairs; *result_in_alt
 // says which holds the result.  ws: radix_sort_workspace_bytes(n) bytes (256 counts per

@@ -52,6 +52,7 @@ import torch
 
 from ..ops.careers import CareerTable
 from ..ops.hindsight import SHARED, Hindsight
+from ..ops.islands import Islands
 from ..ops.native import native
 from ..ops.pairs import PairTable
 from ..ops.rate import RateResult, Roster
@@ -241,6 +242,16 @@ class RecordArena:
             a = int(self.local_row(lo))
             table.add(rec_of(lo, hi), self.rows[a:a + hi - lo], K=self.K)
         return table
+
+    def islands(self, num_players: int, rec_of: Callable[[int, int], torch.Tensor], modes=None) -> Islands:
+        """The islands (``ops/islands.py``, K18) of the match graph of the filled windows, walked
+        as ``careers`` walks them; ``modes`` as ``Islands`` takes them.  On N ranks it covers this
+        rank's blocks only; ``Islands.merge`` unites the ranks' forests."""
+        isl = Islands(num_players, self.device, modes=modes)
+        for lo, hi in self.windows():
+            a = int(self.local_row(lo))
+            isl.add(rec_of(lo, hi), self.rows[a:a + hi - lo], K=self.K)
+        return isl
 
     def scorecard(self, roster0, rec_of: Callable[[int, int], torch.Tensor], **kw) -> Scorecard:
         """The scorecard (``ops/scorecard.py``, K14) of the filled windows, walked as

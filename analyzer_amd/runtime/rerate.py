@@ -48,6 +48,8 @@ streams a long synthetic history through the engine window by window:
         --window 16000000 --records resident --pairs 17,4242  # whom they play with and against (ops/pairs.py)
     python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
         --window 16000000 --records resident --hindsight 17,4242 --hindsight-track ranked  # smoothed curves (ops/hindsight.py)
+    python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
+        --window 16000000 --records resident --islands --islands-ranks 8  # which ratings are comparable (ops/islands.py)
 """
 from __future__ import annotations
 
@@ -65,6 +67,7 @@ import torch
 from ..config import EngineConfig, RaterConfig
 from ..ops import rate as R
 from ..ops.hindsight import track_of
+from ..ops.islands import islands_line
 from ..ops.ladder import build_ladder, track_index
 from ..ops.matchmake import make_lobbies, mode_index, preview_matches, queue_order
 from ..ops.synth import RosterSpec, StreamSpec, make_roster, make_stream
@@ -551,6 +554,13 @@ def main(argv=None) -> int:
                     help="with --pairs: count only the matches of these modes (default: all)")
     ap.add_argument("--pairs-top", type=int, default=None, metavar="N",
                     help="with --pairs: the N most frequent team mates and opponents (default 5)")
+    ap.add_argument("--islands", action="store_true",
+                    help="with --records resident: print the islands of the match graph after the run (one JSON "
+                         "line): how many groups of players are connected through rated matches, and the ten largest")
+    ap.add_argument("--islands-modes", default=None, metavar="MODE[,MODE...]",
+                    help="with --islands: join only through the matches of these modes (default: all)")
+    ap.add_argument("--islands-ranks", type=int, default=None, metavar="N",
+                    help="with --islands: also deal whole islands onto N ranks and print the loads and the imbalance")
     ap.add_argument("--score", default=None, choices=["mode", "shared"],
                     help="with --records resident: score the ratings as predictions on each match's mode track or "
                          "the shared track and print the scorecard after the run (one JSON line; one rank only)")
@@ -621,6 +631,18 @@ def main(argv=None) -> int:
         ap.error("--pairs ids must lie in [0, %d)" % spec.players)
     if pair_top < 0:
         ap.error("--pairs-top must be >= 0")
+    if args.islands and not resident:
+        ap.error("--islands needs --records resident")
+    if (args.islands_modes or args.islands_ranks is not None) and not args.islands:
+        ap.error("--islands-modes and --islands-ranks need --islands")
+    island_modes = [m.strip() for m in (args.islands_modes or "").split(",") if m.strip()] or None
+    try:
+        for m in island_modes or ():
+            mode_index(m)
+    except ValueError as e:
+        ap.error("--islands-modes: %s" % e)
+    if args.islands_ranks is not None and args.islands_ranks < 1:
+        ap.error("--islands-ranks must be >= 1")
     if args.score and not resident:
         ap.error("--score needs --records resident")
     if args.score_modes and not args.score:
@@ -716,6 +738,9 @@ def main(argv=None) -> int:
                                  track=hindsight_track)
         for line in hindsight_lines(curves, hindsight_ids, hindsight_track):
             print(json.dumps(line), flush=True)
+    if args.islands:
+        isl = arena.islands(spec.players, stream_records(spec, arena.device), modes=island_modes)  # this rank's blocks
+        print(json.dumps(dict(islands_line(isl, 10, args.islands_ranks), rank=rank)), flush=True)
     if args.score:
         card = arena.scorecard(roster0, stream_records(spec, arena.device), track=args.score, modes=score_modes)
         print(json.dumps({"scorecard": card.summary()}), flush=True)
