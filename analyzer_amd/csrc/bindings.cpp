@@ -16,6 +16,7 @@
 
 #include "career_core.h"
 #include "common.h"
+#include "expect_core.h"
 #include "gen_core.h"
 #include "hindsight_core.h"
 #include "host.h"
@@ -1036,6 +1037,56 @@ void profiles_add(Tensor table, Tensor cells, Tensor rec, Tensor rows, Tensor st
             "profile_fold");
 }
 
+// K19 (expect.hip; host mirror host.cpp host_expect_add): folds the games of one window -- rec
+// [M, 2K+2] joined with the raw priors [M, 4, 2K] (or [M, 8K]) of priors_add and the pred rows
+// [M, 4] of score_add(keep=True) -- into the player table [P, 24] int32 and the counter bad int64
+// [1] in place (expect_core.h).  Dispatches on the tensors' device; the device path is four
+// stream-ordered steps (keys, sort, fold, stitch) without a host read.
+void expect_add(Tensor table, Tensor bad, Tensor rec, Tensor priors, Tensor pred, int64_t P, int64_t track) {
+  const auto dev = table.device();
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "expect_add: rec must be [M, 2K+2]");
+  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t M = check_rec(rec, K, dev, "expect_add");
+  check_slots(M, K, "expect_add");
+  TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "expect_add: P must fit in int32");
+  check_rows(table, "table", P, ana::kExpectWords, dev, torch::kInt32);
+  check(bad, "bad", torch::kInt64, dev);
+  TORCH_CHECK(bad.numel() == 1, "expect_add: bad must hold one word");
+  check(priors, "priors", torch::kFloat32, dev);
+  TORCH_CHECK((priors.dim() == 2 && priors.size(0) == M && priors.size(1) == 8 * K) ||
+                  (priors.dim() == 3 && priors.size(0) == M && priors.size(1) == 4 && priors.size(2) == 2 * K),
+              "expect_add: priors must be [M, 4, 2K] of rec's matches");
+  check_rows(pred, "pred", M, ana::kPredWords, dev, torch::kInt32);
+  TORCH_CHECK(track == ana::kScoreShared || track == ana::kScoreMode, "expect_add: unknown track ", track);
+  if (M == 0 || P == 0) return;
+  if (!dev.is_cuda()) {
+    TORCH_CHECK(ana::host_expect_add((int)K, rec.data_ptr<int32_t>(), priors.data_ptr<float>(),
+                                     pred.data_ptr<int32_t>(), M, P, (int)track, table.data_ptr<int32_t>(),
+                                     bad.data_ptr<int64_t>()) == 0,
+                "expect_add: bad arguments");
+    return;
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(rec.data_ptr()) % (K % 2 == 0 ? 8 : 16) == 0 &&
+                  reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(priors.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(pred.data_ptr()) % 16 == 0,
+              "expect_add: rec, table, priors and pred must be 16-B aligned");
+  const hipStream_t s = stream_of(table);
+  const int64_t n = M * 2 * K;
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
+  Tensor keys = torch::empty({n}, i32), vals = torch::empty({n}, i32);
+  Tensor terms = torch::empty({n, (int64_t)ana::kExpectTermWords}, i32);
+  check_hip(ana::launch_expect_keys((int)K, rec.data_ptr<int32_t>(), priors.data_ptr<float>(),
+                                    pred.data_ptr<int32_t>(), M, P, (int)track, u32p(keys), u32p(vals),
+                                    terms.data_ptr<int32_t>(), bad.data_ptr<int64_t>(), s),
+            "expect_keys");
+  const auto sorted = sort_pairs_on_stream(keys, vals, n, bit_length(P), s);
+  Tensor fold_edges = torch::empty({(int64_t)ana::expect_edge_bytes(n)}, i32.dtype(torch::kUInt8));
+  check_hip(ana::launch_expect_fold(u32p(sorted[0]), u32p(sorted[1]), terms.data_ptr<int32_t>(), n, (int)K, P,
+                                    table.data_ptr<int32_t>(), fold_edges.data_ptr<uint8_t>(), s),
+            "expect_fold");
+}
+
 // K18 (islands.hip; host mirror host.cpp host_islands_*; island_core.h): the state of an island
 // forest -- parent, slots, credit int32 [P] and ctrl int64 [2] on one device -> that device
 torch::Device check_island_state(const Tensor& parent, const Tensor* slots, const Tensor* credit, const Tensor* ctrl,
@@ -1693,6 +1744,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "place: profiles_add(table, cells, rec, rows, stats, P, track, score, modes, edges)");
   m.attr("PROFILE_WORDS") = ana::kProfileWords;
   m.attr("PROFILE_TILE") = ana::kProfileTile;
+  m.def("expect_add", &expect_add, "K19: fold one window (rec [M, 2K+2] joined with its raw priors [M, 4, 2K] and its "
+        "pred rows [M, 4]) into the player table [P, 24] int32 and the counter bad int64 [1] in place: "
+        "expect_add(table, bad, rec, priors, pred, P, track)");
+  m.attr("EXPECT_WORDS") = ana::kExpectWords;
+  m.attr("EXPECT_TILE") = ana::kExpectTile;
   m.def("priors_add", &priors_add, "K14: the pre-match priors [M, 4 * 2K] fp32 of one window (rec [M, 2K+2] joined with "
         "its packed rows [M, W]) against the chain table [P, 16], advanced in place: priors_add(chain, rec, rows)");
   m.def("hindsight_add", &hindsight_add, "K16: [out [M, 2K, 2] fp32, bad int64 [1]] -- the smoothed (mu, sigma) of one "

@@ -1,4 +1,4 @@
-// The run fold of the per-player tables (K13 careers, K17 profiles): the fold and stitch
+// The run fold of the per-player tables (K13 careers, K17 profiles, K19 expectations): the fold and stitch
 // kernels behind "sort a window's slots by player, fold each player's run into its row".
 // docs/ARCHITECTURE.md ("The shared scans", the run fold) says what it guarantees.
 //

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "career_core.h"
+#include "expect_core.h"
 #include "gen_core.h"
 #include "hindsight_core.h"
 #include "island_core.h"
@@ -814,6 +815,35 @@ int host_score_add(int K, const int32_t* rec, const float* priors, const float* 
   return with_team_size(K, [&](auto k) {
     score_add_k<decltype(k)::value>(rec, priors, rows, W, M, attrs, vst, P, beta2, unknown_sigma, track, modes, table,
                                     pred);
+  }) ? 0 : -1;
+}
+
+// K19: every game in (match, slot) order, its term record added to its player's row
+template <int K>
+static void expect_add_k(const int32_t* rec, const float* priors, const int32_t* pred, int64_t M, int64_t P,
+                         int32_t track, int32_t* table, int64_t* bad) {
+  constexpr int S = 2 * K;
+  const uint32_t* pri = reinterpret_cast<const uint32_t*>(priors);
+  for (int64_t m = 0; m < M; ++m) {
+    const int32_t* r = rec + m * (S + 2);
+    const int32_t* pr = pred + m * kPredWords;
+    const uint32_t mask = expect_game_mask<K>(r, P, (uint32_t)pr[0], (uint32_t)pr[1]);
+    if (!mask) continue;  // the priors are only read for a scored match
+    const uint32_t* src = pri + m * (4 * S);
+    uint32_t mu[S];
+    for (int j = 0; j < S; ++j) mu[j] = expect_raw(track, src[j], src[2 * S + j]);
+    *bad += expect_terms<K>(mask, (uint32_t)pr[1], (uint32_t)pr[2], mu, [&](int j, const int32_t* t) {
+      expect_row_add(table + (int64_t)r[j] * kExpectWords, expect_game(t, profile_won<K>(r, j)));
+    });
+  }
+}
+
+int host_expect_add(int K, const int32_t* rec, const float* priors, const int32_t* pred, int64_t M, int64_t P,
+                    int track, int32_t* table, int64_t* bad) {
+  if (!window_ok(K, 5 * 2 * K + 2, M, P) || (track != kScoreShared && track != kScoreMode) || bad == nullptr)
+    return -1;
+  return with_team_size(K, [&](auto k) {
+    expect_add_k<decltype(k)::value>(rec, priors, pred, M, P, track, table, bad);
   }) ? 0 : -1;
 }
 

@@ -98,6 +98,12 @@ int host_hindsight_add(int K, const int32_t* rec, const float* rows, int64_t W, 
 int host_profiles_add(int K, const int32_t* rec, const float* rows, int64_t W, const float* stats, int64_t M,
                       int64_t P, int track, int score, uint32_t modes, const float* edges, int n_edges,
                       int32_t* table, int64_t* cells);
+// K19 host mirror (expect_core.h): a plain loop over the matches of rec [M][2K+2] joined with the
+// raw priors [M][4 * 2K] and the pred rows [M][kPredWords]; every game's term record is added to
+// its row of table [P][kExpectWords] and the bad own values to *bad, bit-identical to the device.
+// -1: bad arguments.
+int host_expect_add(int K, const int32_t* rec, const float* priors, const int32_t* pred, int64_t M, int64_t P,
+                    int track, int32_t* table, int64_t* bad);
 // K18 host mirror (island_core.h): the plain sequential union-find -- find with path halving,
 // the larger root hooked under the smaller -- over parent / slots / credit [P] and ctrl
 // [kIslandCtrlWords], with the device's liveness rules and counters.  After host_islands_flatten

@@ -218,6 +218,22 @@ int launch_island_flatten(int32_t* parent, int64_t P, int64_t* ctrl, hipStream_t
 int launch_island_census(const int32_t* parent, const int32_t* slots, const int32_t* credit, int64_t P,
                          int64_t* census, int64_t* ctrl, hipStream_t s);
 
+// K19 expectations (expect.hip, expect_core.h): one window rec [M][2K+2] (alignment as for K10)
+// joined with the raw priors [M][4 * 2K] of K14 (field-major, 16-B aligned) and the pred rows
+// [M][kPredWords] of launch_score (16-B aligned), M * 2K <= kMaxSlots.  expect_keys writes per
+// slot i = m * 2K + j the sort key (the player of a game, else P), vals[i] = i | won << 31 and, for
+// a game, its term record at terms[i] (terms [M * 2K][kExpectTermWords] int32, 16-B aligned), and
+// adds the bad own values to *bad; the pairs are sorted with launch_radix_sort_pairs on
+// bit_length(P) bits; expect_fold takes the sorted pairs [n = M * 2K] and adds every player's run
+// to its row of table [P][kExpectWords] (16-B aligned; edges: expect_edge_bytes(n) bytes, 16-B
+// aligned).  track: ScoreTrack.  Everything is stream-ordered and only reads rec, priors and pred.
+constexpr int kExpectTile = 4096;  // sorted elements per workgroup of the fold
+size_t expect_edge_bytes(int64_t n);
+int launch_expect_keys(int K, const int32_t* rec, const float* priors, const int32_t* pred, int64_t M, int64_t P,
+                       int track, uint32_t* keys, uint32_t* vals, int32_t* terms, int64_t* bad, hipStream_t s);
+int launch_expect_fold(const uint32_t* keys, const uint32_t* vals, const int32_t* terms, int64_t n, int K, int64_t P,
+                       int32_t* table, void* edges, hipStream_t s);
+
 // Stable LSD radix sort of (key, value) pairs on the low ``bits`` key bits
 // (radix_sort.hip).  Ping-pongs between the two buffer pairs; *result_in_alt
 // says which holds the result.  ws: radix_sort_workspace_bytes(n) bytes (256 counts per

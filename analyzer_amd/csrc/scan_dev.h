@@ -1,9 +1,9 @@
 // Workgroup scans of the analytics kernels (K10 select, K13 careers, K14 scorecard, K15 pairs,
-// K16 hindsight, K17 profiles),
+// K16 hindsight, K17 profiles, K19 expectations),
 // device only: the segmented scan by key behind the fold / tile / stitch kernels, and the
 // block sum and block offset behind the count / emit kernels.  docs/ARCHITECTURE.md ("The
 // shared scans") says what they guarantee and how a new feature plugs in.  The fold and stitch
-// kernels of K13 and K17 are fold_dev.h on top of the segmented scan.
+// kernels of K13, K17 and K19 are fold_dev.h on top of the segmented scan.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -9,3 +9,4 @@ from .matchmake import (Balanced, Preview, balance_lobbies, fill_winners, make_l
                         preview_matches)
 from .hindsight import Hindsight  # noqa: F401
 from .islands import Islands  # noqa: F401
+from .expectations import Expectations  # noqa: F401

@@ -143,19 +143,28 @@ class Scorecard:
         """Score one window: its records ``rec`` [M, 2K+2] and packed output rows ``rows``
         [M, W] (``RateResult.packed``).  Windows are added in chronological order.
         ``keep``: return the per-match ``Prediction``."""
+        preds = [pred for _, _, _, pred in self.scored_chunks(rec, rows, keep)]
+        return self.prediction(preds) if keep else None
+
+    def scored_chunks(self, rec: torch.Tensor, rows: torch.Tensor, keep: bool = True):
+        """``add`` chunk by chunk: for each chunk of at most ``max_slots`` slots, in order, the
+        match range and what the kernels made of it, ``(a, b, priors [b - a, 8K], pred rows
+        [b - a, 4] int32)`` (``pred`` empty unless ``keep``).  The chain and the table advance
+        as the chunks are drawn (K19 folds each chunk's priors and pred before the next)."""
         K = _window(rec, rows)
         M = int(rec.shape[0])
         step = max(1, self.max_slots // (2 * K))
-        preds = []
         for a in range(0, M, step):
             b = min(M, a + step)
             priors = native().priors_add(self.chain, rec[a:b], rows[a:b])
-            preds.append(native().score_add(self.table, rec[a:b], priors, rows[a:b], self.attrs, self.vst,
-                                            self.num_players, float(self.cfg.beta) ** 2,
-                                            float(self.cfg.unknown_player_sigma), TRACKS.index(self.track),
-                                            self.modes, bool(keep)))
-        if not keep:
-            return None
+            pred = native().score_add(self.table, rec[a:b], priors, rows[a:b], self.attrs, self.vst,
+                                      self.num_players, float(self.cfg.beta) ** 2,
+                                      float(self.cfg.unknown_player_sigma), TRACKS.index(self.track),
+                                      self.modes, bool(keep))
+            yield a, b, priors, pred
+
+    def prediction(self, preds) -> Prediction:
+        """The ``Prediction`` of the pred rows of consecutive chunks."""
         out = preds[0] if len(preds) == 1 else torch.cat(preds) if preds else \
             torch.empty((0, 4), dtype=torch.int32, device=self.device)
         flags = out[:, 0].contiguous()

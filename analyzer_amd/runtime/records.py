@@ -31,6 +31,9 @@ for K = 4, 5).  ``records="resident"`` keeps them where the executor writes them
   ``Scorecard``, csrc/score.hip, K14): the belief before every match is reconstructed from
   the rows and the roster the history started from, and the win probability it gives is
   scored against the outcome.  One rank only.
+* ``expectations(roster0, rec_of)`` holds every player up against those predictions
+  (``ops/expectations.py`` ``Expectations``, csrc/expect.hip, K19): expected against actual
+  wins, and the strength of team mates against opponents.  One rank only.
 * ``hindsight(num_players, rec_of, players)`` smooths every player's skill curve backwards
   over the filled windows (``ops/hindsight.py`` ``Hindsight``, csrc/hindsight.hip, K16) and
   returns the filtered and the smoothed curve of the listed players.  One rank only.
@@ -51,6 +54,7 @@ from typing import Callable, Dict, Iterator, Optional, Sequence, Tuple, Union
 import torch
 
 from ..ops.careers import CareerTable
+from ..ops.expectations import Expectations
 from ..ops.hindsight import SHARED, Hindsight
 from ..ops.islands import Islands
 from ..ops.native import native
@@ -267,6 +271,20 @@ class RecordArena:
             a = int(self.local_row(lo))
             card.add(rec_of(lo, hi), self.rows[a:a + hi - lo])
         return card
+
+    def expectations(self, roster0, rec_of: Callable[[int, int], torch.Tensor], **kw) -> Expectations:
+        """The expectation table (``ops/expectations.py``, K19) of the filled windows, walked
+        as ``scorecard`` walks them, from the same ``roster0``; ``kw``: ``track``, ``modes``,
+        ``cfg`` of ``Expectations``.  Its card chains the whole history in order, so on N > 1
+        ranks this raises."""
+        if self.size > 1:
+            raise ValueError("expectations chain the whole history in order: they need a one-rank arena, this is "
+                             "rank %d of %d" % (self.rank, self.size))
+        exp = Expectations(roster0, **kw)
+        for lo, hi in self.windows():
+            a = int(self.local_row(lo))
+            exp.add(rec_of(lo, hi), self.rows[a:a + hi - lo])
+        return exp
 
     def hindsight(self, num_players: int, rec_of: Callable[[int, int], torch.Tensor], players: Sequence[int],
                   **kw) -> Dict[str, torch.Tensor]:

@@ -50,6 +50,8 @@ streams a long synthetic history through the engine window by window:
         --window 16000000 --records resident --hindsight 17,4242 --hindsight-track ranked  # smoothed curves (ops/hindsight.py)
     python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
         --window 16000000 --records resident --islands --islands-ranks 8  # which ratings are comparable (ops/islands.py)
+    python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
+        --window 16000000 --records resident --expect 17,4242 --expect-outliers 20  # wins against the odds (ops/expectations.py)
 """
 from __future__ import annotations
 
@@ -66,6 +68,7 @@ import torch
 
 from ..config import EngineConfig, RaterConfig
 from ..ops import rate as R
+from ..ops.expectations import expectation_lines, outliers_line
 from ..ops.hindsight import track_of
 from ..ops.islands import islands_line
 from ..ops.ladder import build_ladder, track_index
@@ -566,6 +569,16 @@ def main(argv=None) -> int:
                          "the shared track and print the scorecard after the run (one JSON line; one rank only)")
     ap.add_argument("--score-modes", default=None, metavar="MODE[,MODE...]",
                     help="with --score: count only the matches of these modes (default: all)")
+    ap.add_argument("--expect", default=None, metavar="ID[,ID...]",
+                    help="with --records resident: hold each player up against the pre-match predictions after the "
+                         "run (JSON lines; one rank only): expected against actual wins, z score, and the strength "
+                         "of team mates against opponents; then one line of the strongest outliers")
+    ap.add_argument("--expect-track", default=None, choices=["mode", "shared"],
+                    help="with --expect: predict on each match's mode track (default) or the shared track")
+    ap.add_argument("--expect-modes", default=None, metavar="MODE[,MODE...]",
+                    help="with --expect: count only the matches of these modes (default: all)")
+    ap.add_argument("--expect-outliers", type=int, default=None, metavar="N",
+                    help="with --expect: the N players furthest above their expectation (default 10)")
     ap.add_argument("--export-records", default=None, metavar="PATH",
                     help="with --records resident: write the arena to PATH (+ PATH.json; .rN appended on N ranks)")
     ap.add_argument("--arena-free-bytes", type=float, default=None,
@@ -655,6 +668,24 @@ def main(argv=None) -> int:
             mode_index(m)
     except ValueError as e:
         ap.error("--score-modes: %s" % e)
+    if args.expect and not resident:
+        ap.error("--expect needs --records resident")
+    if (args.expect_track or args.expect_modes or args.expect_outliers is not None) and not args.expect:
+        ap.error("--expect-track, --expect-modes and --expect-outliers need --expect")
+    if args.expect and size > 1:
+        ap.error("--expect chains the whole history in order: it runs on one rank")
+    expect_modes = [m.strip() for m in (args.expect_modes or "").split(",") if m.strip()] or None
+    expect_top = 10 if args.expect_outliers is None else args.expect_outliers
+    try:
+        expect_ids = [int(p) for p in (args.expect or "").split(",") if p.strip()]
+        for m in expect_modes or ():
+            mode_index(m)
+    except ValueError as e:
+        ap.error("--expect: %s" % e)
+    if any(p < 0 or p >= spec.players for p in expect_ids):
+        ap.error("--expect ids must lie in [0, %d)" % spec.players)
+    if expect_top < 0:
+        ap.error("--expect-outliers must be >= 0")
     if args.ladder_rank and not args.ladder:
         ap.error("--ladder-rank needs --ladder")
     ladder_tracks = [t.strip() for t in (args.ladder or "").split(",") if t.strip()]
@@ -690,7 +721,9 @@ def main(argv=None) -> int:
                       % (plan["arena_bytes_per_rank"], plan["roster_bytes"], plan["left_bytes"], plan["free_bytes"],
                          plan["reserve_bytes"]), file=sys.stderr, flush=True)
                 return 2
-            roster0 = start_roster(spec, args.checkpoint_dir, torch.device(args.device or dev)) if args.score else None
+            roster0 = None
+            if args.score or expect_ids:
+                roster0 = start_roster(spec, args.checkpoint_dir, torch.device(args.device or dev))
             res, roster, arena = rerate_resident(spec, args.device or dev, args.checkpoint_dir, plan=plan,
                                                  checkpoint_every=args.checkpoint_every,
                                                  fault_kill_after=args.fault_kill_after, comm_dtype=args.comm_dtype,
@@ -744,6 +777,12 @@ def main(argv=None) -> int:
     if args.score:
         card = arena.scorecard(roster0, stream_records(spec, arena.device), track=args.score, modes=score_modes)
         print(json.dumps({"scorecard": card.summary()}), flush=True)
+    if expect_ids:
+        exp = arena.expectations(roster0, stream_records(spec, arena.device), track=args.expect_track or "mode",
+                                 modes=expect_modes)
+        for line in expectation_lines(exp, expect_ids):
+            print(json.dumps(line), flush=True)
+        print(json.dumps(outliers_line(exp, expect_top)), flush=True)
     if ladder_tracks and rank == 0:  # the roster is replicated after the last merge
         for line in ladder_lines(roster, ladder_tracks, args.ladder_top, ladder_ids):
             print(json.dumps(line), flush=True)
