@@ -63,6 +63,9 @@ int64_t check_rows_view(const Tensor& t, const char* name, torch::ScalarType dt,
   return rows > 1 ? t.stride(0) : inner;
 }
 
+// the device's vector loads and stores need their operands aligned
+bool aligned(const Tensor& t, int bytes) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0; }
+
 hipStream_t stream_of(const Tensor& t) {
   return at::hip::getCurrentHIPStream(t.device().index()).stream();
 }
@@ -82,6 +85,12 @@ int64_t check_rec(const Tensor& rec, int64_t K, const torch::Device& dev, const 
   return rec.size(0);
 }
 
+// the team size K of a match stream rec [M, 2K+2], from its width (check_rec holds K to 1..5)
+int64_t team_size_of(const Tensor& rec, const char* what) {
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, what, ": rec must be [M, 2K+2]");
+  return (rec.size(1) - 2) / 2;
+}
+
 // one window as K10, K13, K14 and K15 take it: rec [M, 2K+2] and its packed output rows [M, W]
 // on dev, aligned for the device's vector loads -> M
 int64_t check_window(const Tensor& rec, const Tensor& rows, int64_t K, const torch::Device& dev, const char* what) {
@@ -90,9 +99,7 @@ int64_t check_window(const Tensor& rec, const Tensor& rows, int64_t K, const tor
   TORCH_CHECK(rows.dim() == 2 && rows.size(0) == M && rows.size(1) >= 10 * K + 2 && rows.size(1) % 4 == 0, what,
               ": rows must be the packed [M, W] output rows of rec's matches");
   if (dev.is_cuda())
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(rec.data_ptr()) % (K % 2 == 0 ? 8 : 16) == 0 &&
-                    reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0,
-                what, ": rec and rows must be 16-B aligned");
+    TORCH_CHECK(aligned(rec, K % 2 == 0 ? 8 : 16) && aligned(rows, 16), what, ": rec and rows must be 16-B aligned");
   return M;
 }
 
@@ -154,6 +161,20 @@ std::vector<Tensor> sort_pairs_on_stream(Tensor keys, Tensor vals, int64_t n, in
                                          ws.data_ptr<uint8_t>(), &in_alt, s),
             "radix sort");
   return in_alt ? std::vector<Tensor>{kalt, valt} : std::vector<Tensor>{keys, vals};
+}
+
+// What the per-player tables (K13, K14, K16, K17, K19) do with a window's n = M * 2K slots before
+// their scan: run_keys(keys, vals) fills the sort pairs, the stable sort by player follows on the
+// same stream (P == 0: no player, nothing to sort), and the scan's edge buffer is allocated.
+struct SortedSlots { Tensor keys, vals, edges; };
+template <class RunKeys>
+SortedSlots sort_by_player(int64_t n, int64_t P, size_t edge_bytes, const torch::Device& dev, hipStream_t s,
+                           RunKeys&& run_keys) {
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
+  Tensor keys = torch::empty({n}, i32), vals = torch::empty({n}, i32);
+  run_keys(u32p(keys), u32p(vals));
+  const auto sorted = P > 0 ? sort_pairs_on_stream(keys, vals, n, bit_length(P), s) : std::vector<Tensor>{keys, vals};
+  return {sorted[0], sorted[1], torch::empty({(int64_t)edge_bytes}, i32.dtype(torch::kUInt8))};
 }
 
 // --------------------------------------------------------------------- K7
@@ -558,7 +579,7 @@ static void check_operands(const Tensor& msg, const Tensor& cnt, int64_t P, cons
   TORCH_CHECK(cnt.device() == dev && cnt.scalar_type() == torch::kInt32 && cnt.dim() == 2 && cnt.size(0) == P &&
                   cnt.size(1) == 1,
               "cnt must be [P, 1] int32 on the state's device");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(msg.data_ptr()) % 4 == 0, "msg rows must be 4-B aligned");
+  TORCH_CHECK(aligned(msg, 4), "msg rows must be 4-B aligned");
 }
 
 static Tensor pack_touch(const Tensor& lohi) {  // [P, 2] float fields -> [P, 1] int32
@@ -873,7 +894,7 @@ void records_digest(Tensor rows, int64_t K, Tensor scratch, Tensor out, const c1
                   256 % (rows.size(1) / 4) == 0,
               "records_digest: rows must be the packed [M, W] output rows (W / 4 a divisor of 256)");
   TORCH_CHECK(out.numel() == 3 + 10 * K, "records_digest: out needs 3 + 10K doubles");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0, "records_digest: rows must be 16-B aligned");
+  TORCH_CHECK(aligned(rows, 16), "records_digest: rows must be 16-B aligned");
   TORCH_CHECK(dev.is_cuda(), "records_digest: device rows (the host path is runtime/rerate.py window_digest)");
   TORCH_CHECK((size_t)scratch.numel() >= ana::records_digest_scratch_doubles((int)K), "records_digest: scratch too small");
   int64_t* h = nullptr;
@@ -943,8 +964,7 @@ Tensor tile_offsets(Tensor counts) {
 std::pair<int64_t, int64_t> check_fold_args(const Tensor& table, int64_t words, const Tensor& rec, const Tensor& rows,
                                             int64_t P, int64_t track, int64_t score, int64_t modes, const char* what) {
   const auto dev = table.device();
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, what, ": rec must be [M, 2K+2]");
-  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t K = team_size_of(rec, what);
   const int64_t M = check_window(rec, rows, K, dev, what);
   check_slots(M, K, what);
   TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, what, ": P must fit in int32");
@@ -972,19 +992,17 @@ void careers_add(Tensor table, Tensor rec, Tensor rows, int64_t base, int64_t P,
                 "careers_add: bad arguments");
     return;
   }
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0, "careers_add: table must be 16-B aligned");
+  TORCH_CHECK(aligned(table, 16), "careers_add: table must be 16-B aligned");
   const hipStream_t s = stream_of(table);
   const int64_t n = M * 2 * K;
-  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
-  Tensor keys = torch::empty({n}, i32), vals = torch::empty({n}, i32);
-  Tensor events = torch::empty({n, (int64_t)ana::kCareerEventWords}, i32);
-  check_hip(ana::launch_career_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
-                                    (int)track, (int)score, (uint32_t)modes, u32p(keys), u32p(vals), u32p(events), s),
-            "career_keys");
-  const auto sorted = sort_pairs_on_stream(keys, vals, n, bit_length(P), s);
-  Tensor edges = torch::empty({(int64_t)ana::career_edge_bytes(n)}, i32.dtype(torch::kUInt8));
-  check_hip(ana::launch_career_fold(u32p(sorted[0]), u32p(sorted[1]), u32p(events), n, (int)K, base, P,
-                                    table.data_ptr<int32_t>(), edges.data_ptr<uint8_t>(), s),
+  Tensor events = torch::empty({n, (int64_t)ana::kCareerEventWords}, rec.options());
+  const auto sorted = sort_by_player(n, P, ana::career_edge_bytes(n), dev, s, [&](uint32_t* keys, uint32_t* vals) {
+    check_hip(ana::launch_career_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                      (int)track, (int)score, (uint32_t)modes, keys, vals, u32p(events), s),
+              "career_keys");
+  });
+  check_hip(ana::launch_career_fold(u32p(sorted.keys), u32p(sorted.vals), u32p(events), n, (int)K, base, P,
+                                    table.data_ptr<int32_t>(), sorted.edges.data_ptr<uint8_t>(), s),
             "career_fold");
 }
 
@@ -1019,21 +1037,17 @@ void profiles_add(Tensor table, Tensor cells, Tensor rec, Tensor rows, Tensor st
                 "profiles_add: bad arguments");
     return;
   }
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(stats.data_ptr()) % 16 == 0,
-              "profiles_add: table and stats must be 16-B aligned");
+  TORCH_CHECK(aligned(table, 16) && aligned(stats, 16), "profiles_add: table and stats must be 16-B aligned");
   const hipStream_t s = stream_of(table);
   const int64_t n = M * 2 * K;
-  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
-  Tensor keys = torch::empty({n}, i32), vals = torch::empty({n}, i32);
-  check_hip(ana::launch_profile_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1),
-                                     stats.data_ptr<float>(), M, P, (int)track, (int)score, (uint32_t)modes, ep,
-                                     n_edges, u32p(keys), u32p(vals), cells.data_ptr<int64_t>(), s),
-            "profile_keys");
-  const auto sorted = sort_pairs_on_stream(keys, vals, n, bit_length(P), s);
-  Tensor fold_edges = torch::empty({(int64_t)ana::profile_edge_bytes(n)}, i32.dtype(torch::kUInt8));
-  check_hip(ana::launch_profile_fold(u32p(sorted[0]), u32p(sorted[1]), stats.data_ptr<float>(), n, (int)K, P,
-                                     table.data_ptr<int32_t>(), fold_edges.data_ptr<uint8_t>(), s),
+  const auto sorted = sort_by_player(n, P, ana::profile_edge_bytes(n), dev, s, [&](uint32_t* keys, uint32_t* vals) {
+    check_hip(ana::launch_profile_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1),
+                                       stats.data_ptr<float>(), M, P, (int)track, (int)score, (uint32_t)modes, ep,
+                                       n_edges, keys, vals, cells.data_ptr<int64_t>(), s),
+              "profile_keys");
+  });
+  check_hip(ana::launch_profile_fold(u32p(sorted.keys), u32p(sorted.vals), stats.data_ptr<float>(), n, (int)K, P,
+                                     table.data_ptr<int32_t>(), sorted.edges.data_ptr<uint8_t>(), s),
             "profile_fold");
 }
 
@@ -1044,8 +1058,7 @@ void profiles_add(Tensor table, Tensor cells, Tensor rec, Tensor rows, Tensor st
 // stream-ordered steps (keys, sort, fold, stitch) without a host read.
 void expect_add(Tensor table, Tensor bad, Tensor rec, Tensor priors, Tensor pred, int64_t P, int64_t track) {
   const auto dev = table.device();
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "expect_add: rec must be [M, 2K+2]");
-  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t K = team_size_of(rec, "expect_add");
   const int64_t M = check_rec(rec, K, dev, "expect_add");
   check_slots(M, K, "expect_add");
   TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "expect_add: P must fit in int32");
@@ -1066,24 +1079,19 @@ void expect_add(Tensor table, Tensor bad, Tensor rec, Tensor priors, Tensor pred
                 "expect_add: bad arguments");
     return;
   }
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(rec.data_ptr()) % (K % 2 == 0 ? 8 : 16) == 0 &&
-                  reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(priors.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(pred.data_ptr()) % 16 == 0,
+  TORCH_CHECK(aligned(rec, K % 2 == 0 ? 8 : 16) && aligned(table, 16) && aligned(priors, 16) && aligned(pred, 16),
               "expect_add: rec, table, priors and pred must be 16-B aligned");
   const hipStream_t s = stream_of(table);
   const int64_t n = M * 2 * K;
-  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
-  Tensor keys = torch::empty({n}, i32), vals = torch::empty({n}, i32);
-  Tensor terms = torch::empty({n, (int64_t)ana::kExpectTermWords}, i32);
-  check_hip(ana::launch_expect_keys((int)K, rec.data_ptr<int32_t>(), priors.data_ptr<float>(),
-                                    pred.data_ptr<int32_t>(), M, P, (int)track, u32p(keys), u32p(vals),
-                                    terms.data_ptr<int32_t>(), bad.data_ptr<int64_t>(), s),
-            "expect_keys");
-  const auto sorted = sort_pairs_on_stream(keys, vals, n, bit_length(P), s);
-  Tensor fold_edges = torch::empty({(int64_t)ana::expect_edge_bytes(n)}, i32.dtype(torch::kUInt8));
-  check_hip(ana::launch_expect_fold(u32p(sorted[0]), u32p(sorted[1]), terms.data_ptr<int32_t>(), n, (int)K, P,
-                                    table.data_ptr<int32_t>(), fold_edges.data_ptr<uint8_t>(), s),
+  Tensor terms = torch::empty({n, (int64_t)ana::kExpectTermWords}, rec.options());
+  const auto sorted = sort_by_player(n, P, ana::expect_edge_bytes(n), dev, s, [&](uint32_t* keys, uint32_t* vals) {
+    check_hip(ana::launch_expect_keys((int)K, rec.data_ptr<int32_t>(), priors.data_ptr<float>(),
+                                      pred.data_ptr<int32_t>(), M, P, (int)track, keys, vals, terms.data_ptr<int32_t>(),
+                                      bad.data_ptr<int64_t>(), s),
+              "expect_keys");
+  });
+  check_hip(ana::launch_expect_fold(u32p(sorted.keys), u32p(sorted.vals), terms.data_ptr<int32_t>(), n, (int)K, P,
+                                    table.data_ptr<int32_t>(), sorted.edges.data_ptr<uint8_t>(), s),
             "expect_fold");
 }
 
@@ -1115,8 +1123,7 @@ torch::Device check_island_state(const Tensor& parent, const Tensor* slots, cons
 void islands_add(Tensor parent, Tensor slots, Tensor credit, Tensor ctrl, Tensor rec, Tensor rows, int64_t P,
                  int64_t modes) {
   const auto dev = check_island_state(parent, &slots, &credit, &ctrl, P, "islands_add");
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "islands_add: rec must be [M, 2K+2]");
-  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t K = team_size_of(rec, "islands_add");
   const int64_t M = check_window(rec, rows, K, dev, "islands_add");
   check_slots(M, K, "islands_add");
   TORCH_CHECK(modes >= 0 && (modes & ~(int64_t)ana::kIslandAllModes) == 0,
@@ -1193,8 +1200,7 @@ Tensor islands_census(Tensor parent, Tensor slots, Tensor credit, Tensor ctrl, i
 // summaries, stitch, apply, fields) without a host read.
 Tensor priors_add(Tensor chain, Tensor rec, Tensor rows) {
   const auto dev = chain.device();
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "priors_add: rec must be [M, 2K+2]");
-  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t K = team_size_of(rec, "priors_add");
   const int64_t M = check_window(rec, rows, K, dev, "priors_add");
   check_slots(M, K, "priors_add");
   TORCH_CHECK(chain.dim() == 2, "priors_add: chain must be [P, 16]");
@@ -1211,17 +1217,15 @@ Tensor priors_add(Tensor chain, Tensor rec, Tensor rows) {
   }
   const hipStream_t s = stream_of(chain);
   const int64_t n = M * 2 * K;
-  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
-  Tensor keys = torch::empty({n}, i32), vals = torch::empty({n}, i32);
-  Tensor events = torch::empty({n, (int64_t)ana::kPriorEventWords}, i32);
-  Tensor slot_priors = torch::empty({n, 4}, i32);  // the prior words slot-major, 16 B per slot
-  check_hip(ana::launch_prior_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
-                                   u32p(keys), u32p(vals), u32p(events), u32p(slot_priors), s),
-            "prior_keys");
-  const auto sorted = P > 0 ? sort_pairs_on_stream(keys, vals, n, bit_length(P), s) : std::vector<Tensor>{keys, vals};
-  Tensor edges = torch::empty({(int64_t)ana::prior_edge_bytes(n)}, i32.dtype(torch::kUInt8));
-  check_hip(ana::launch_prior_scan(u32p(sorted[0]), u32p(sorted[1]), u32p(events), n, (int)K, P,
-                                   chain.data_ptr<float>(), edges.data_ptr<uint8_t>(), u32p(slot_priors),
+  Tensor events = torch::empty({n, (int64_t)ana::kPriorEventWords}, rec.options());
+  Tensor slot_priors = torch::empty({n, 4}, rec.options());  // the prior words slot-major, 16 B per slot
+  const auto sorted = sort_by_player(n, P, ana::prior_edge_bytes(n), dev, s, [&](uint32_t* keys, uint32_t* vals) {
+    check_hip(ana::launch_prior_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P, keys,
+                                     vals, u32p(events), u32p(slot_priors), s),
+              "prior_keys");
+  });
+  check_hip(ana::launch_prior_scan(u32p(sorted.keys), u32p(sorted.vals), u32p(events), n, (int)K, P,
+                                   chain.data_ptr<float>(), sorted.edges.data_ptr<uint8_t>(), u32p(slot_priors),
                                    priors.data_ptr<float>(), s),
             "prior_scan");
   return priors;
@@ -1234,8 +1238,7 @@ Tensor priors_add(Tensor chain, Tensor rec, Tensor rows) {
 // is five stream-ordered steps (keys, sort, summaries, stitch, apply) without a host read.
 std::vector<Tensor> hindsight_add(Tensor carry, Tensor rec, Tensor rows, double tau, int64_t track, int64_t mode) {
   const auto dev = carry.device();
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "hindsight_add: rec must be [M, 2K+2]");
-  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t K = team_size_of(rec, "hindsight_add");
   const int64_t M = check_window(rec, rows, K, dev, "hindsight_add");
   check_slots(M, K, "hindsight_add");
   TORCH_CHECK(carry.dim() == 2, "hindsight_add: carry must be [P, 2]");
@@ -1261,19 +1264,17 @@ std::vector<Tensor> hindsight_add(Tensor carry, Tensor rec, Tensor rows, double 
   if (M == 0) return {out, bad.to(torch::kInt64)};
   const hipStream_t s = stream_of(carry);
   const int64_t n = M * 2 * K;
-  Tensor keys = torch::empty({n}, i32), vals = torch::empty({n}, i32);
   Tensor events = torch::empty({n, 2}, i32);
-  check_hip(ana::launch_hindsight_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
-                                       (int)track, (int)mode, u32p(keys), u32p(vals), u32p(events),
-                                       out.data_ptr<float>(), bad.data_ptr<int32_t>(), s),
-            "hindsight_keys");
-  if (P > 0) {
-    const auto sorted = sort_pairs_on_stream(keys, vals, n, bit_length(P), s);
-    Tensor edges = torch::empty({(int64_t)ana::hindsight_edge_bytes(n)}, i32.dtype(torch::kUInt8));
-    check_hip(ana::launch_hindsight_scan(u32p(sorted[0]), u32p(sorted[1]), u32p(events), n, (int)K, P, tau2,
-                                         carry.data_ptr<double>(), edges.data_ptr<uint8_t>(), out.data_ptr<float>(), s),
-              "hindsight_scan");
-  }
+  const auto sorted = sort_by_player(n, P, ana::hindsight_edge_bytes(n), dev, s, [&](uint32_t* keys, uint32_t* vals) {
+    check_hip(ana::launch_hindsight_keys((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                         (int)track, (int)mode, keys, vals, u32p(events), out.data_ptr<float>(),
+                                         bad.data_ptr<int32_t>(), s),
+              "hindsight_keys");
+  });
+  check_hip(ana::launch_hindsight_scan(u32p(sorted.keys), u32p(sorted.vals), u32p(events), n, (int)K, P, tau2,
+                                       carry.data_ptr<double>(), sorted.edges.data_ptr<uint8_t>(),
+                                       out.data_ptr<float>(), s),
+            "hindsight_scan");
   return {out, bad.to(torch::kInt64)};
 }
 
@@ -1283,8 +1284,7 @@ std::vector<Tensor> hindsight_add(Tensor carry, Tensor rec, Tensor rows, double 
 Tensor score_add(Tensor table, Tensor rec, Tensor priors, Tensor rows, c10::optional<Tensor> attrs, Tensor vst,
                  int64_t P, double beta2, double unknown_sigma, int64_t track, int64_t modes, bool keep) {
   const auto dev = table.device();
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "score_add: rec must be [M, 2K+2]");
-  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t K = team_size_of(rec, "score_add");
   const int64_t M = check_window(rec, rows, K, dev, "score_add");
   check_slots(M, K, "score_add");
   check(table, "table", torch::kInt64, dev);
@@ -1390,8 +1390,7 @@ std::tuple<Tensor, Tensor> pair_sort_reduce(Tensor ka, Tensor kb, Tensor bkeep, 
 std::tuple<Tensor, Tensor> pairs_window(Tensor rec, Tensor rows, int64_t P, int64_t modes,
                                         const c10::optional<Tensor>& bitmap) {
   const auto dev = rec.device();
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) >= 4 && rec.size(1) % 2 == 0, "pairs_window: rec must be [M, 2K+2]");
-  const int64_t K = (rec.size(1) - 2) / 2;
+  const int64_t K = team_size_of(rec, "pairs_window");
   const int64_t M = check_window(rec, rows, K, dev, "pairs_window");
   TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "pairs_window: P must fit in int32");
   TORCH_CHECK(modes >= 0 && (modes & ~(int64_t)ana::kPairAllModes) == 0,
@@ -1512,7 +1511,7 @@ std::vector<Tensor> ladder(Tensor state, int64_t mask, int64_t score, double max
     }
     return out;
   }
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(state.data_ptr()) % 16 == 0, "ladder: state must be 16-B aligned");
+  TORCH_CHECK(aligned(state, 16), "ladder: state must be 16-B aligned");
   const hipStream_t s = stream_of(state);
   const int64_t stride = (P + 31) / 32 * 32;  // every track's keys start on a 128-B line
   Tensor keys = torch::empty({T, stride}, i32), ids = torch::empty({T, stride}, i32);
@@ -1543,7 +1542,7 @@ const float* matchmake_roster(const Tensor& state, const c10::optional<Tensor>& 
   const int64_t P = check_state(state, dev, what);
   check_vst(vst, dev, what);
   TORCH_CHECK(P <= 0x7fffffffLL, what, ": P must be below 2^31");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(state.data_ptr()) % 16 == 0, what, ": state must be 16-B aligned");
+  TORCH_CHECK(aligned(state, 16), what, ": state must be 16-B aligned");
   if (!attrs.has_value() || !attrs->defined()) return nullptr;
   const float* at = check_attrs(*attrs, P, dev, what);
   TORCH_CHECK(reinterpret_cast<uintptr_t>(at) % 16 == 0, what, ": attrs must be 16-B aligned");

@@ -11,9 +11,9 @@
 // and each of its two kernels is one call: RunFold<F, kThreads, kTile>::fold with a gather
 // callable (sort value -> the run of that one game) and ::stitch.
 //
-// K14 (score.hip prior_tile_kernel<*>, prior_stitch_kernel) does not belong here: its scan is
-// exclusive and seeded from a carry array over three kernels, a different algorithm that also
-// happens to use tiles and edges.
+// K14 and K16 (score.hip prior_tile_kernel<*>, prior_stitch_kernel; hindsight.hip likewise) do
+// not belong here but in chain_dev.h: their scan is seeded from the row it ends in, over three
+// kernels, and who owns a row differs -- here a row is only ever added to.
 #pragma once
 
 #include <hip/hip_runtime.h>

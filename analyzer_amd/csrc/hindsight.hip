@@ -15,64 +15,41 @@
 //              one per workgroup that has any).
 //   sort       launch_radix_sort_pairs on bit_length(P) bits: stable, so each player's elements
 //              come out newest first.
-//   summaries  one workgroup per tile of kHindsightTile sorted elements: the inclusive SegScan
-//              of the elements' maps.  The newest element of a player in the window whose
-//              carry row is NaN is the chain's newest, a constant; every other element is its
-//              map.  The runs of the tile's first and last key, the only ones that can go on
-//              in a neighbour tile, leave their totals (without anything behind them) in
-//              edges[2 * tile + 0 / 1].
-//   stitch     one workgroup: the same scan over the 2 * tiles edges in tile order.  The first
-//              edge of a key, its newest stretch, contributes the key's carry row as a seed
-//              (the identity for a NaN row), every other edge the total of the edge before
-//              it, so seeds[e] is what lies behind edge e's stretch; the last edge of a key
-//              stores the new carry row.
-//   apply      the summaries scan again, now seeded: the first element of a key in the tile
-//              takes seeds[2 * tile] (the tile's first key), seeds[2 * tile + 1] (its last
-//              key) or, for a run strictly inside the tile, the key's carry row.  Every
+//   summaries  one workgroup per tile of kHindsightTile sorted elements: the inclusive scan of
+//              the elements' maps.  The newest element of a player in the window whose carry
+//              row is NaN is the chain's newest, a constant; every other element is its map.
+//              The totals of the tile's first and last key (without anything behind them) go
+//              to edges[2 * tile + 0 / 1].
+//   stitch     one workgroup over the 2 * tiles edges, seeded from the carry rows (the identity
+//              for a NaN row): seeds[e] is what lies behind edge e's stretch; a key's last
+//              edge stores its new carry row.
+//   apply      the summaries scan again, seeded from seeds or, for a run strictly inside the
+//              tile, from the carry row, which the run's last (oldest) element stores.  Every
 //              element stores its 8-B (mh, sqrt(Ph)) as fp32 at out[slot], slot-major
-//              [M][2K][2], which is the public layout; the last (oldest) element of an inner
-//              run stores its carry row.
+//              [M][2K][2], which is the public layout.
 //
-// The table in place, without a race.  summaries only reads carry rows, and every later step
-// starts after it has finished.  From then on a key's row has one reader, the step that seeds
-// the key's newest element in the window, and one writer, the step that holds its oldest, and
-// the written value depends on the read one through the scan.  A run inside one tile that is
-// neither the tile's first nor last key is read and written by that tile's apply workgroup
-// alone: the newest element's lane loads the row, the scan (shuffles, LDS, barriers) carries it
-// to the oldest element's lane, which stores; no other workgroup sees the key.  Every other run
-// -- across tiles or touching a tile's end -- is in the edges, and its row is read and written
-// by the stitch workgroup alone, first edge to last edge through the same scan; apply never
-// touches that row and takes what lies behind from seeds, which stitch filled before it
-// overwrote the row.  Whether a seed is "nothing" survives the overwrite as the identity in
-// seeds (hindsight_core.h: B == 1 against the B == 0 of every constant).
+// The last three are the chained scan of chain_dev.h over HsChain below; its header argues why
+// the carry rows are updated in place without a race (its "first" is a player's newest element,
+// its "last" the oldest).  That a seed is "nothing" survives in seeds as the identity (B == 1).
 //
 // Built with -ffp-contract=off: every fp64 operation is the one written.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 
+#include "chain_dev.h"
 #include "common.h"
 #include "hindsight_core.h"
 #include "kernels.h"
 #include "record_dev.h"
-#include "scan_dev.h"
 
 namespace ana {
 
 namespace {
 
 constexpr int kHsThreads = 256;
-constexpr int kHsIters = kHindsightTile / kHsThreads;
-static_assert(kHindsightTile % kHsThreads == 0, "a tile is a whole number of iterations");
 
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
-
-// an edge or a seed: its key and a map, 32 B
-struct HsEdge {
-  uint32_t key, pad;
-  HsMap s;
-};
-static_assert(sizeof(HsEdge) == 32 && alignof(HsEdge) == 8, "an edge is four 8-B pieces");
 
 template <int K>
 __global__ void __launch_bounds__(kHsThreads) hindsight_keys_kernel(
@@ -136,129 +113,77 @@ __global__ void __launch_bounds__(kHsThreads) hindsight_keys_kernel(
   if (threadIdx.x == 0 && wg_bad) atomicAdd(bad, wg_bad);
 }
 
-struct HsOps {
-  static __device__ __forceinline__ HsMap combine(const HsMap& x, const HsMap& y) { return hs_scan_combine(x, y); }
+// The feature of the chained scan (chain_dev.h), newest first: a lane's scanned state is the
+// composition of the maps of its key from its element to the newest, behind it the seed.  A run
+// ends in a constant, so its total is the smoothed (mh, Ph) of its oldest element.
+struct HsChain {
+  typedef HsMap State;
+  const v2u* __restrict__ events;
+  int64_t n;
+  double tau2;
+  v2u* __restrict__ out;
+
   static __device__ __forceinline__ HsMap identity() { return hs_identity(); }
+  static __device__ __forceinline__ HsMap combine(const HsMap& x, const HsMap& y) { return hs_scan_combine(x, y); }
+  static __device__ __forceinline__ HsMap seed(const double* __restrict__ carry, uint32_t key) {
+    return hs_seed_of_row(carry[(int64_t)key * 2], carry[(int64_t)key * 2 + 1]);
+  }
+  static __device__ __forceinline__ void row_store(double* __restrict__ carry, uint32_t key, const HsMap& s) {
+    carry[(int64_t)key * 2] = s.A;
+    carry[(int64_t)key * 2 + 1] = s.C;
+  }
+
+  // make(mu, sigma) of the filtered values of the element in slot
+  template <class Make>
+  __device__ __forceinline__ HsMap term(uint32_t slot, Make&& make) const {
+    if ((int64_t)slot >= n) return hs_identity();  // slot < n always: a permutation
+    const v2u e = events[slot];
+    return make(__uint_as_float(e[0]), __uint_as_float(e[1]));
+  }
+  __device__ __forceinline__ HsMap next(uint32_t, uint32_t slot) const {
+    return term(slot, [&](float mu, float sigma) { return hs_element(mu, sigma, tau2); });
+  }
+  __device__ __forceinline__ HsMap first(uint32_t slot, const HsMap& seed) const {
+    return term(slot, [&](float mu, float sigma) { return hs_seeded(mu, sigma, tau2, seed); });
+  }
+  // With a NaN carry row nothing lies behind the key's newest element of the window: it is the
+  // chain's newest, a constant.  A row that is set is applied by stitch or apply, not here.
+  __device__ __forceinline__ HsMap open(uint32_t slot, uint32_t key, bool newest, const double* carry) const {
+    const double behind = carry[(int64_t)key * 2];
+    return term(slot, [&](float mu, float sigma) {
+      return newest && behind != behind ? hs_newest(mu, sigma) : hs_element(mu, sigma, tau2);
+    });
+  }
+  __device__ __forceinline__ HsMap total(uint32_t, const HsMap& s) const { return s; }
+  __device__ __forceinline__ void emit(uint32_t slot, const HsMap& s) const {
+    if ((int64_t)slot >= n) return;
+    v2u x;
+    x[0] = __float_as_uint((float)s.A);
+    x[1] = __float_as_uint((float)sqrt(s.C));
+    out[slot] = x;
+  }
 };
-// on return from step a lane's state is the composition of the maps of its key from the lane's
-// element to the newest one this workgroup saw
-typedef SegScan<kHsThreads, HsMap, HsOps> HsScan;
+typedef ChainScan<HsChain, kHsThreads, kHindsightTile> HsScan;
+typedef HsScan::Edge HsEdge;
+static_assert(sizeof(HsEdge) == 32 && offsetof(HsEdge, s) == 8, "an edge or a seed: [key, -, map], four 8-B pieces");
 
-__device__ __forceinline__ HsMap carry_seed(const double* __restrict__ carry, uint32_t key) {
-  const double* row = carry + (int64_t)key * 2;
-  return hs_seed_of_row(row[0], row[1]);
-}
-
-// s ends in a constant: the smoothed (mh, Ph) of its oldest element
-__device__ __forceinline__ void carry_store(double* __restrict__ carry, uint32_t key, const HsMap& s) {
-  double* row = carry + (int64_t)key * 2;
-  row[0] = s.A;
-  row[1] = s.C;
-}
-
-__device__ __forceinline__ void edge_store(HsEdge* __restrict__ edges, int64_t e, uint32_t key, const HsMap& s) {
-  edges[e].key = key;
-  state_store(&edges[e].s, s);
-}
-
-// summaries (APPLY = false) and apply (APPLY = true) over one tile of the sorted pairs
-template <bool APPLY>
+template <bool APPLY>  // summaries (false) and apply (true)
 __global__ void __launch_bounds__(kHsThreads) hindsight_tile_kernel(
     const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, const v2u* __restrict__ events, int64_t n,
     uint32_t P, double tau2, double* __restrict__ carry, HsEdge* __restrict__ edges,
     const HsEdge* __restrict__ seeds, v2u* __restrict__ out) {
-  __shared__ HsScan::Lds lds;
-  const int t = threadIdx.x;
-  const int64_t tile = blockIdx.x;
-  const int64_t lo = tile * kHindsightTile;
-  const int64_t hi = lo + kHindsightTile < n ? lo + kHindsightTile : n;
-  const uint32_t head = keys[lo], tailkey = keys[hi - 1];
-  if (head >= P) {  // sorted: nothing but slots that are no elements from here on
-    if (!APPLY && t < 2) edges[2 * tile + t].key = kNoKey;
-    return;
-  }
-  HsScan::init(lds);
-  for (int it = 0; it < kHsIters; ++it) {
-    const int64_t i = lo + (int64_t)it * kHsThreads + t;
-    if (lo + (int64_t)it * kHsThreads >= hi) break;  // uniform over the workgroup
-    const bool valid = i < hi;
-    const uint32_t key = valid ? keys[i] : kNoKey;
-    const bool first = !(valid && i > lo && keys[i - 1] == key);  // of its key in this tile
-    const bool last = valid && (i + 1 == hi || keys[i + 1] != key);
-    const bool edge_run = key == head || key == tailkey;
-    const uint32_t slot = valid ? vals[i] : 0u;
-    const bool has = valid && key < P && (int64_t)slot < n;  // slot < n always: a permutation
-    HsMap s = hs_identity();
-    if (has) {
-      const v2u e = events[slot];
-      const float mu = __uint_as_float(e[0]), sigma = __uint_as_float(e[1]);
-      if (!first) {
-        s = hs_element(mu, sigma, tau2);
-      } else if (APPLY) {
-        const HsMap seed = key == head      ? state_load(&seeds[2 * tile].s)
-                           : key == tailkey ? state_load(&seeds[2 * tile + 1].s)
-                                            : carry_seed(carry, key);
-        s = hs_seeded(mu, sigma, tau2, seed);
-      } else {
-        // The key's newest element in the window, unless its run began in the tile before.
-        // With a NaN carry row nothing lies behind it: it is the chain's newest, a constant.
-        // A row that is set is applied by stitch or apply, not here.
-        const bool newest = i == 0 || keys[i - 1] != key;
-        const double behind = carry[(int64_t)key * 2];
-        s = newest && behind != behind ? hs_newest(mu, sigma) : hs_element(mu, sigma, tau2);
-      }
-    }
-    HsScan::step(lds, it, key, s);  // the element and everything newer of its key in the tile
-    if (APPLY) {
-      if (has) {
-        v2u x;
-        x[0] = __float_as_uint((float)s.A);
-        x[1] = __float_as_uint((float)sqrt(s.C));
-        out[slot] = x;
-        if (last && !edge_run) carry_store(carry, key, s);
-      }
-    } else if (valid && (i + 1 == hi || (last && key == head))) {
-      // the last element of the first key, and the tile's last element
-      if (key == head) {
-        edge_store(edges, 2 * tile, key, s);
-        if (i + 1 == hi) edge_store(edges, 2 * tile + 1, key, hs_identity());
-      } else {
-        edge_store(edges, 2 * tile + 1, has ? key : kNoKey, s);
-      }
-    }
-  }
+  HsScan::tile<APPLY>(keys, vals, n, P, carry, edges, seeds, HsChain{events, n, tau2, out});
 }
 
-// one workgroup over the edges [E] in tile order
 __global__ void __launch_bounds__(kHsThreads) hindsight_stitch_kernel(const HsEdge* __restrict__ edges, int64_t E,
                                                                       uint32_t P, double* __restrict__ carry,
                                                                       HsEdge* __restrict__ seeds) {
-  __shared__ HsScan::Lds lds;
-  const int t = threadIdx.x;
-  HsScan::init(lds);
-  const int iters = (int)((E + kHsThreads - 1) / kHsThreads);
-  for (int it = 0; it < iters; ++it) {
-    const int64_t e = (int64_t)it * kHsThreads + t;
-    const uint32_t key = e < E ? edges[e].key : kNoKey;
-    const bool has = key < P;
-    const bool first = !(e > 0 && e < E && edges[e - 1].key == key);
-    const bool last = !(e + 1 < E && edges[e + 1].key == key);
-    HsMap s = hs_identity();
-    if (has) s = first ? carry_seed(carry, key) : state_load(&edges[e - 1].s);
-    HsScan::step(lds, it, key, s);  // what lies behind edge e's stretch
-    if (has) {
-      state_store(&seeds[e].s, s);
-      // a run always ends in a constant: its newest element, or the carry row behind it
-      if (last) carry_store(carry, key, hs_scan_combine(s, state_load(&edges[e].s)));
-    }
-  }
+  HsScan::stitch(edges, E, P, carry, seeds);
 }
 
 }  // namespace
 
-static int64_t hindsight_tiles(int64_t n) { return (n + kHindsightTile - 1) / kHindsightTile; }
-// edges and seeds, 2 * tiles entries each
-size_t hindsight_edge_bytes(int64_t n) { return (size_t)(2 * 2 * hindsight_tiles(n)) * sizeof(HsEdge); }
+size_t hindsight_edge_bytes(int64_t n) { return HsScan::edge_bytes(n); }
 
 int launch_hindsight_keys(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, int track,
                           int mode, uint32_t* keys, uint32_t* vals, uint32_t* events, float* out, int32_t* bad,
@@ -283,7 +208,7 @@ int launch_hindsight_scan(const uint32_t* keys, const uint32_t* vals, const uint
       reinterpret_cast<uintptr_t>(out) % 8 != 0 || reinterpret_cast<uintptr_t>(edges) % 8 != 0)
     return (int)hipErrorInvalidValue;
   if (n == 0 || P == 0) return 0;
-  const int64_t tiles = hindsight_tiles(n);
+  const int64_t tiles = HsScan::tiles(n);
   HsEdge* e = static_cast<HsEdge*>(edges);
   HsEdge* seeds = e + 2 * tiles;
   const v2u* ev = reinterpret_cast<const v2u*>(events);

@@ -2,8 +2,8 @@
 // K16 hindsight, K17 profiles, K19 expectations),
 // device only: the segmented scan by key behind the fold / tile / stitch kernels, and the
 // block sum and block offset behind the count / emit kernels.  docs/ARCHITECTURE.md ("The
-// shared scans") says what they guarantee and how a new feature plugs in.  The fold and stitch
-// kernels of K13, K17 and K19 are fold_dev.h on top of the segmented scan.
+// shared scans") says what they guarantee and how a new feature plugs in.  On the segmented
+// scan sit fold_dev.h (K13, K17, K19: fold and stitch) and chain_dev.h (K14, K16: tile and stitch).
 #pragma once
 
 #include <hip/hip_runtime.h>

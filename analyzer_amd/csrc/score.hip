@@ -15,35 +15,21 @@
 //   sort       launch_radix_sort_pairs on bit_length(P) bits: stable, so each player's slots
 //              come out in (match, slot) order.
 //   summaries  one workgroup per tile of kPriorTile sorted elements.  The exclusive scan is
-//              run as the inclusive scan of scan_dev.h over shifted terms: element i
-//              contributes the write of element i - 1 of the same key, so the scanned value
-//              is the state before i and
-//              one 16-B gather per element feeds it.  The runs of the tile's first and last
-//              key, the only ones that can go on in a neighbour tile, leave their totals
-//              (without any starting state) in edges[2 * tile + 0 / 1].
-//   stitch     one workgroup: the same scan over the 2 * tiles edges in tile order.  The
-//              first edge of a key contributes the key's chain row, so carry[e] is the state
-//              before edge e's stretch, starting state included; the last edge of a key
-//              stores the state after the window into the chain row.
-//   apply      the summaries scan again, now seeded: the first element of a key in the tile
-//              contributes carry[2 * tile] (the tile's first key), carry[2 * tile + 1] (its
-//              last key) or, for a run strictly inside the tile, the key's chain row.  Every
-//              live element stores the four prior words of its mode as one 16-B slot-major
-//              entry; the last element of an inner run stores the run's final state into
-//              its chain row.
+//              run as the inclusive scan over shifted terms: element i contributes the write of
+//              element i - 1 of the same key, so the scanned value is the state before i and
+//              one 16-B gather per element feeds it.  The totals of the tile's first and last
+//              key (without any starting state) go to edges[2 * tile + 0 / 1].
+//   stitch     one workgroup over the 2 * tiles edges, seeded from the chain rows: carry[e] is
+//              the state before edge e's stretch; a key's last edge stores its chain row.
+//   apply      the summaries scan again, seeded from carry or, for a run strictly inside the
+//              tile, from the chain row, which the run's last element stores.  Every live
+//              element stores the four prior words of its mode as one 16-B slot-major entry.
 //   fields     one lane per match: the slot-major entries [M][2K][4] to the field-major
 //              priors [M][4][2K], 16-B loads and stores (four scattered 4-B stores per slot
 //              in apply instead cost more than this pass and its buffer).
 //
-// The table in place, without a race.  A key's chain row has one reader, the globally first
-// element of the key, and one writer, the globally last, and the written value depends on the
-// read one through the scan.  A run inside one tile that is neither the tile's first nor last
-// key is read and written by that tile's apply workgroup alone: the first element's lane
-// loads the row, the scan (shuffles, LDS, barriers) carries it to the last element's lane,
-// which stores; no other workgroup sees the key.  Every other run -- across tiles or touching
-// a tile's end -- is in the edges, and its row is read and written by the stitch workgroup
-// alone, first edge to last edge through the same scan; apply never touches that row and
-// takes the starting state from carry, which stitch filled before it overwrote the row.
+// summaries, stitch and apply are the chained scan of chain_dev.h over PriorChain below; its
+// header has the argument why the chain rows are read and written in place without a race.
 //
 // Score.  One lane per match over rec, priors, the row's status byte and (behind a NULL
 // shared track only) attrs: player_prior per slot, then d and sum sigma^2 in preview_kernel's
@@ -56,10 +42,10 @@
 
 #include <stdint.h>
 
+#include "chain_dev.h"
 #include "common.h"
 #include "kernels.h"
 #include "record_dev.h"
-#include "scan_dev.h"
 #include "score_core.h"
 
 namespace ana {
@@ -67,11 +53,6 @@ namespace ana {
 namespace {
 
 constexpr int kPriorThreads = 256;
-constexpr int kPriorIters = kPriorTile / kPriorThreads;
-static_assert(kPriorTile % kPriorThreads == 0, "a tile is a whole number of iterations");
-// an edge or a carry: [key, mask, w[14]], 64 B
-constexpr int kEdgeWords = 16;
-static_assert(sizeof(PriorState) == 4 * (kEdgeWords - 1), "an edge holds a key and a state");
 constexpr int kScoreThreads = 256;
 
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
@@ -131,103 +112,58 @@ __global__ void __launch_bounds__(kPriorThreads) prior_keys_kernel(
   }
 }
 
-struct PriorOps {
-  static __device__ __forceinline__ PriorState combine(const PriorState& a, const PriorState& b) {
-    return prior_combine(a, b);
-  }
+// The feature of the chained scan (chain_dev.h): an exclusive scan under "the later write
+// wins", run as the inclusive one over shifted terms.  An element contributes the write of the
+// one before it, so its scanned state is the one before it; a run's total adds its own write.
+struct PriorChain {
+  typedef PriorState State;
+  const v4u* __restrict__ events;
+  int64_t n;
+  v4u* __restrict__ slot_priors;
+
   static __device__ __forceinline__ PriorState identity() { return prior_none(); }
-};
-// on return from step a lane's state covers the terms of its key from the first one this
-// workgroup saw up to the lane's
-typedef SegScan<kPriorThreads, PriorState, PriorOps> PriorScan;
-
-// the state of the edge or carry entry e: the words behind its key
-__device__ __forceinline__ const PriorState* edge_state(const uint32_t* entries, int64_t e) {
-  return reinterpret_cast<const PriorState*>(entries + e * kEdgeWords + 1);
-}
-__device__ __forceinline__ PriorState* edge_state(uint32_t* entries, int64_t e) {
-  return reinterpret_cast<PriorState*>(entries + e * kEdgeWords + 1);
-}
-
-// the write of the slot with sort value v (prior_none() when it does not write)
-__device__ __forceinline__ PriorState slot_write(uint32_t v, const v4u* __restrict__ events, int64_t n) {
-  const uint32_t slot = v & kPriorSlotMask;
-  if (!(v & kPriorWriteBit) || (int64_t)slot >= n) return prior_none();  // slot < n always: a permutation
-  const v4u e = events[slot];
-  return prior_write((int)((v >> kPriorModeShift) & 7u), e[0], e[1], e[2], e[3]);
-}
-
-__device__ __forceinline__ void chain_store(uint32_t* __restrict__ chain, uint32_t key, const PriorState& s) {
-  uint32_t* row = chain + (int64_t)key * kBaseFloats;
+  static __device__ __forceinline__ State combine(const State& a, const State& b) { return prior_combine(a, b); }
+  static __device__ __forceinline__ PriorState seed(const uint32_t* __restrict__ chain, uint32_t key) {
+    return prior_from_chain(chain + (int64_t)key * kBaseFloats);
+  }
+  static __device__ __forceinline__ void row_store(uint32_t* __restrict__ chain, uint32_t key, const PriorState& s) {
+    uint32_t* row = chain + (int64_t)key * kBaseFloats;
 #pragma unroll
-  for (int i = 0; i < 2 * kTracks; ++i) row[i] = s.w[i];
-}
+    for (int i = 0; i < 2 * kTracks; ++i) row[i] = s.w[i];
+  }
 
-__device__ __forceinline__ void edge_store(uint32_t* __restrict__ edges, int64_t e, uint32_t key, const PriorState& s) {
-  edges[e * kEdgeWords] = key;
-  state_store(edge_state(edges, e), s);
-}
+  // the write of the slot with sort value v (prior_none() when it does not write)
+  __device__ __forceinline__ PriorState write(uint32_t v) const {
+    const uint32_t slot = v & kPriorSlotMask;
+    if (!(v & kPriorWriteBit) || (int64_t)slot >= n) return prior_none();  // slot < n always: a permutation
+    const v4u e = events[slot];
+    return prior_write((int)((v >> kPriorModeShift) & 7u), e[0], e[1], e[2], e[3]);
+  }
+  __device__ __forceinline__ PriorState next(uint32_t prev, uint32_t) const { return write(prev); }
+  __device__ __forceinline__ PriorState first(uint32_t, const PriorState& seed) const { return seed; }
+  __device__ __forceinline__ PriorState open(uint32_t, uint32_t, bool, const uint32_t*) const { return prior_none(); }
+  __device__ __forceinline__ State total(uint32_t v, const State& s) const { return prior_combine(s, write(v)); }
+  // the four prior words of the element's mode from the state before it, as one 16-B store
+  __device__ __forceinline__ void emit(uint32_t v, const PriorState& s) const {
+    const uint32_t slot = v & kPriorSlotMask;
+    if ((int64_t)slot >= n) return;
+    uint32_t w[4];
+    prior_pick(s, (int)((v >> kPriorModeShift) & 7u), w);
+    v4u x;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) x[f] = w[f];
+    slot_priors[slot] = x;
+  }
+};
+typedef ChainScan<PriorChain, kPriorThreads, kPriorTile> PriorScan;
+static_assert(sizeof(PriorScan::Edge) == 64 && offsetof(PriorScan::Edge, s) == 4, "an edge: [key, mask, w[14]]");
 
-// summaries (APPLY = false) and apply (APPLY = true) over one tile of the sorted pairs
-template <bool APPLY>
+template <bool APPLY>  // summaries (false) and apply (true)
 __global__ void __launch_bounds__(kPriorThreads) prior_tile_kernel(
     const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, const v4u* __restrict__ events, int64_t n,
-    uint32_t P, uint32_t* __restrict__ chain, uint32_t* __restrict__ edges,
-    const uint32_t* __restrict__ carry, v4u* __restrict__ slot_priors) {
-  __shared__ PriorScan::Lds lds;
-  const int t = threadIdx.x;
-  const int64_t tile = blockIdx.x;
-  const int64_t lo = tile * kPriorTile;
-  const int64_t hi = lo + kPriorTile < n ? lo + kPriorTile : n;
-  const uint32_t head = keys[lo], tailkey = keys[hi - 1];
-  if (head >= P) {  // sorted: nothing but slots that are not live from here on
-    if (!APPLY && t < 2) edges[(2 * tile + t) * kEdgeWords] = kNoKey;
-    return;
-  }
-  PriorScan::init(lds);
-  for (int it = 0; it < kPriorIters; ++it) {
-    const int64_t i = lo + (int64_t)it * kPriorThreads + t;
-    if (lo + (int64_t)it * kPriorThreads >= hi) break;  // uniform over the workgroup
-    const bool valid = i < hi;
-    const uint32_t key = valid ? keys[i] : kNoKey;
-    const bool has = valid && key < P;
-    const bool first = !(valid && i > lo && keys[i - 1] == key);  // of its key in this tile
-    const bool last = valid && (i + 1 == hi || keys[i + 1] != key);
-    const bool edge_run = key == head || key == tailkey;
-    PriorState s = prior_none();
-    if (has) {
-      if (!first) {
-        s = slot_write(vals[i - 1], events, n);
-      } else if (APPLY) {
-        s = key == head      ? state_load(edge_state(carry, 2 * tile))
-            : key == tailkey ? state_load(edge_state(carry, 2 * tile + 1))
-                             : prior_from_chain(chain + (int64_t)key * kBaseFloats);
-      }
-    }
-    PriorScan::step(lds, it, key, s);  // the state before element i
-    const uint32_t v = has ? vals[i] : 0u;
-    if (APPLY) {
-      const uint32_t slot = v & kPriorSlotMask;
-      if (has && (int64_t)slot < n) {
-        uint32_t w[4];
-        prior_pick(s, (int)((v >> kPriorModeShift) & 7u), w);
-        v4u x;
-#pragma unroll
-        for (int f = 0; f < 4; ++f) x[f] = w[f];
-        slot_priors[slot] = x;  // one 16-B store; prior_fields_kernel lays them out by field
-      }
-      if (has && last && !edge_run) chain_store(chain, key, prior_combine(s, slot_write(v, events, n)));
-    } else if (valid && (i + 1 == hi || (last && key == head))) {
-      // the last element of the first key, and the tile's last element
-      const PriorState total = has ? prior_combine(s, slot_write(v, events, n)) : prior_none();
-      if (key == head) {
-        edge_store(edges, 2 * tile, key, total);
-        if (i + 1 == hi) edge_store(edges, 2 * tile + 1, key, prior_none());
-      } else {
-        edge_store(edges, 2 * tile + 1, has ? key : kNoKey, total);
-      }
-    }
-  }
+    uint32_t P, uint32_t* __restrict__ chain, PriorScan::Edge* __restrict__ edges,
+    const PriorScan::Edge* __restrict__ carry, v4u* __restrict__ slot_priors) {
+  PriorScan::tile<APPLY>(keys, vals, n, P, chain, edges, carry, PriorChain{events, n, slot_priors});
 }
 
 // slot-major prior words [M][2K][4] to the field-major priors [M][4][2K]: one lane per match,
@@ -254,29 +190,11 @@ __global__ void __launch_bounds__(kPriorThreads) prior_fields_kernel(const v4u* 
   }
 }
 
-// one workgroup over the edges [E] in tile order
-__global__ void __launch_bounds__(kPriorThreads) prior_stitch_kernel(const uint32_t* __restrict__ edges, int64_t E,
-                                                                     uint32_t P, uint32_t* __restrict__ chain,
-                                                                     uint32_t* __restrict__ carry) {
-  __shared__ PriorScan::Lds lds;
-  const int t = threadIdx.x;
-  PriorScan::init(lds);
-  const int iters = (int)((E + kPriorThreads - 1) / kPriorThreads);
-  for (int it = 0; it < iters; ++it) {
-    const int64_t e = (int64_t)it * kPriorThreads + t;
-    const uint32_t key = e < E ? edges[e * kEdgeWords] : kNoKey;
-    const bool has = key < P;
-    const bool first = !(e > 0 && e < E && edges[(e - 1) * kEdgeWords] == key);
-    const bool last = !(e + 1 < E && edges[(e + 1) * kEdgeWords] == key);
-    PriorState s = prior_none();
-    if (has)
-      s = first ? prior_from_chain(chain + (int64_t)key * kBaseFloats) : state_load(edge_state(edges, e - 1));
-    PriorScan::step(lds, it, key, s);  // the state before edge e's stretch
-    if (has) {
-      state_store(edge_state(carry, e), s);
-      if (last) chain_store(chain, key, prior_combine(s, state_load(edge_state(edges, e))));
-    }
-  }
+__global__ void __launch_bounds__(kPriorThreads) prior_stitch_kernel(const PriorScan::Edge* __restrict__ edges,
+                                                                     int64_t E, uint32_t P,
+                                                                     uint32_t* __restrict__ chain,
+                                                                     PriorScan::Edge* __restrict__ carry) {
+  PriorScan::stitch(edges, E, P, chain, carry);
 }
 
 // What the priors pr [4][2K] of one record resolve to, as preview_kernel (matchmake.hip) sees
@@ -435,9 +353,7 @@ int launch_nlog2_q20(const uint32_t* bits, int64_t n, int64_t* out, hipStream_t 
   return (int)hipGetLastError();
 }
 
-static int64_t prior_tiles(int64_t n) { return (n + kPriorTile - 1) / kPriorTile; }
-// edges and carry, 2 * tiles entries each
-size_t prior_edge_bytes(int64_t n) { return (size_t)(2 * 2 * prior_tiles(n) * kEdgeWords) * 4; }
+size_t prior_edge_bytes(int64_t n) { return PriorScan::edge_bytes(n); }
 
 int launch_prior_keys(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, uint32_t* keys,
                       uint32_t* vals, uint32_t* events, uint32_t* slot_priors, hipStream_t s) {
@@ -460,9 +376,9 @@ int launch_prior_scan(const uint32_t* keys, const uint32_t* vals, const uint32_t
   if (n == 0) return 0;
   v4u* sp = reinterpret_cast<v4u*>(slot_priors);
   if (P > 0) {
-    const int64_t tiles = prior_tiles(n);
-    uint32_t* e = static_cast<uint32_t*>(edges);
-    uint32_t* carry = e + 2 * tiles * kEdgeWords;
+    const int64_t tiles = PriorScan::tiles(n);
+    PriorScan::Edge* e = static_cast<PriorScan::Edge*>(edges);
+    PriorScan::Edge* carry = e + 2 * tiles;
     uint32_t* ch = reinterpret_cast<uint32_t*>(chain);
     const v4u* ev = reinterpret_cast<const v4u*>(events);
     hipLaunchKernelGGL(prior_tile_kernel<false>, dim3((unsigned)tiles), dim3(kPriorThreads), 0, s, keys, vals, ev, n,

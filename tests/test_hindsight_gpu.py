@@ -47,6 +47,18 @@ def test_stitch_takes_two_iterations(gpu_device):
     H.check_stitch(gpu_device, mirror=H.run("cpu", rec, rows, P))
 
 
+@pytest.mark.parametrize("window", [H.tile_edges, H.stitch], ids=["tile_edges", "stitch"])
+def test_same_bits_on_every_run(gpu_device, window):
+    """No atomics on floats and one owner per carry row: a second run gives the first one's bits,
+    NaNs included, in ``out`` (fp32), ``carry`` (fp64) and ``bad``."""
+    rec, rows, P = window()
+    first = H.run(gpu_device, rec, rows, P)
+    again = H.run(gpu_device, rec, rows, P)
+    assert np.array_equal(first[0].view(np.uint32), again[0].view(np.uint32))
+    assert np.array_equal(first[1].view(np.uint64), again[1].view(np.uint64))
+    assert first[2] == again[2]
+
+
 def test_window_cuts(gpu_device):
     H.check_window_cuts(gpu_device)
 
