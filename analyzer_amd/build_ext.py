@@ -29,7 +29,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 HIP_SOURCES = ["kernels.hip", "radix_sort.hip", "dataflow.hip", "sweep.hip", "telemetry.hip", "levels.hip",
                "digest.hip", "select.hip", "ladder.hip", "matchmake.hip", "career.hip", "score.hip",
-               "pairs.hip", "scan.hip", "profile.hip", "hindsight.hip", "islands.hip", "expect.hip"]
+               "pairs.hip", "scan.hip", "profile.hip", "hindsight.hip", "islands.hip", "expect.hip", "ttt.hip"]
 # per-file device flags.  The executor's divisions/sqrt take the 1-ulp hardware
 # paths (v_rcp_f32 instead of the ~10-instruction IEEE division expansion: -9%
 # static instructions); NaN/Inf semantics are untouched (no -ffinite-math-only),
@@ -51,6 +51,9 @@ HIP_FLAGS["hindsight.hip"] = ["-ffp-contract=off"]
 # an expectation's rint(p * 2^24) and rint(mu * 256) are the products the host mirror forms
 # (csrc/expect_core.h)
 HIP_FLAGS["expect.hip"] = ["-ffp-contract=off"]
+# the through-time messages and scan elements are fp64 operations as written, the host mirror's
+# (csrc/ttt_core.h)
+HIP_FLAGS["ttt.hip"] = ["-ffp-contract=off"]
 CPP_SOURCES = ["host.cpp", "ingest.cpp", "batch_host.cpp", "telemetry_file.cpp", "bindings.cpp"]
 
 

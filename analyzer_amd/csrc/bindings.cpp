@@ -29,6 +29,7 @@
 #include "profile_core.h"
 #include "score_core.h"
 #include "select_core.h"
+#include "ttt_core.h"
 
 namespace {
 
@@ -1278,6 +1279,92 @@ std::vector<Tensor> hindsight_add(Tensor carry, Tensor rec, Tensor rows, double 
   return {out, bad.to(torch::kInt64)};
 }
 
+// K20 (ttt.hip; host mirror host.cpp host_ttt_fit; ttt_core.h): the joint re-estimate of one
+// history -- rec [M, 2K+2] joined with its packed rows [M, W] and its K14 priors [M, 4, 2K] (or
+// [M, 8K]) -- after at most `sweeps` sweeps and a final chain pass; tol >= 0 stops after the chain
+// pass whose residual is below it (one host read per sweep then, none otherwise).  Returns [out
+// [M, 2K, 2] fp32 (NaN: no element), residual fp64 [sweeps run], cav [M * 2K, 2] fp64 (the
+// cavities of the last chain pass), msg [M * 2K, 2] fp64 (the messages it ran on), counters int64
+// [3] (bad, flat, inconsistent)].  Dispatches on rec's device.
+std::vector<Tensor> ttt_fit(Tensor rec, Tensor rows, Tensor priors, c10::optional<Tensor> attrs, Tensor vst, int64_t P,
+                            double beta2, double tau, double unknown_sigma, int64_t track, int64_t mode,
+                            int64_t sweeps, double tol, double damping) {
+  const auto dev = rec.device();
+  const int64_t K = team_size_of(rec, "ttt_fit");
+  const int64_t M = check_window(rec, rows, K, dev, "ttt_fit");
+  check_slots(M, K, "ttt_fit");
+  TORCH_CHECK(P >= 0 && P <= 0x7fffffffLL, "ttt_fit: P must fit in int32");
+  check(priors, "priors", torch::kFloat32, dev);
+  TORCH_CHECK((priors.dim() == 2 && priors.size(0) == M && priors.size(1) == 8 * K) ||
+                  (priors.dim() == 3 && priors.size(0) == M && priors.size(1) == 4 && priors.size(2) == 2 * K),
+              "ttt_fit: priors must be [M, 4, 2K] of rec's matches");
+  check_vst(vst, dev, "ttt_fit");
+  const float* at = nullptr;
+  if (attrs.has_value() && attrs->defined()) at = check_attrs(*attrs, P, dev, "ttt_fit");
+  TORCH_CHECK(std::isfinite(tau) && tau >= 0.0, "ttt_fit: tau must be finite and >= 0, got ", tau);
+  TORCH_CHECK(std::isfinite(beta2) && beta2 >= 0.0, "ttt_fit: beta2 must be finite and >= 0, got ", beta2);
+  TORCH_CHECK(track == ana::kHsShared || track == ana::kHsMode, "ttt_fit: unknown track ", track);
+  TORCH_CHECK(track != ana::kHsMode || (mode >= 0 && mode < ana::kModes), "ttt_fit: a mode track needs a mode 0..5, "
+              "got ", mode);
+  TORCH_CHECK(sweeps >= 0 && sweeps <= (1 << 20), "ttt_fit: sweeps must be 0..2^20, got ", sweeps);
+  TORCH_CHECK(damping > 0.0 && damping <= 1.0, "ttt_fit: damping must lie in (0, 1], got ", damping);
+  TORCH_CHECK(!(tol != tol), "ttt_fit: tol is a NaN");
+  const double tau2 = tau * tau;
+  const int64_t n = M * 2 * K;
+  const auto f64 = torch::TensorOptions().dtype(torch::kFloat64).device(dev);
+  Tensor out = torch::empty({M, 2 * K, 2}, rows.options());
+  Tensor cav = torch::empty({n, 2}, f64), msg = torch::empty({n, 2}, f64);
+  if (!dev.is_cuda()) {
+    Tensor resid = torch::zeros({sweeps}, f64), counters = torch::zeros({(int64_t)ana::kTttCounters}, torch::kInt64);
+    const int64_t run = ana::host_ttt_fit(
+        (int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P, priors.data_ptr<float>(), at,
+        vst.data_ptr<float>(), (float)unknown_sigma, beta2, tau2, (int)track, (int)mode, sweeps, tol, damping,
+        out.data_ptr<float>(), cav.data_ptr<double>(), msg.data_ptr<double>(), resid.data_ptr<double>(),
+        counters.data_ptr<int64_t>());
+    TORCH_CHECK(run >= 0, "ttt_fit: bad arguments");
+    return {out, resid.narrow(0, 0, run), cav, msg, counters};
+  }
+  TORCH_CHECK(aligned(priors, 16) && (at == nullptr || aligned(*attrs, 16)), "ttt_fit: priors and attrs must be 16-B "
+              "aligned");
+  const hipStream_t s = stream_of(rec);
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
+  cav.zero_();
+  msg.zero_();
+  Tensor prior = torch::empty({n, 2}, f64), fwd = torch::empty({n, 2}, f64), mu64 = torch::empty({n}, f64);
+  Tensor mword = torch::empty({M}, i32), counters = torch::zeros({(int64_t)ana::kTttCounters}, i32);
+  Tensor bits = torch::zeros({sweeps + 1}, i32.dtype(torch::kInt64));  // bits[k]: the residual of chain pass k
+  Tensor kf = torch::empty({n}, i32), vf = torch::empty({n}, i32), kb = torch::empty({n}, i32),
+         vb = torch::empty({n}, i32);
+  check_hip(ana::launch_ttt_setup((int)K, rec.data_ptr<int32_t>(), rows.data_ptr<float>(), rows.size(1), M, P,
+                                  priors.data_ptr<float>(), at, vst.data_ptr<float>(), (float)unknown_sigma, (int)track,
+                                  (int)mode, tau2, u32p(kf), u32p(vf), u32p(kb), u32p(vb), msg.data_ptr<double>(),
+                                  prior.data_ptr<double>(), out.data_ptr<float>(), u32p(mword),
+                                  counters.data_ptr<int32_t>(), s),
+            "ttt_setup");
+  std::vector<Tensor> fs = {kf, vf}, bs = {kb, vb};
+  if (P > 0 && n > 0) {
+    fs = sort_pairs_on_stream(kf, vf, n, bit_length(P), s);
+    bs = sort_pairs_on_stream(kb, vb, n, bit_length(P), s);
+  }
+  Tensor edges = torch::empty({(int64_t)ana::ttt_edge_bytes(n)}, i32.dtype(torch::kUInt8));
+  int64_t run = 0;
+  for (int64_t k = 0;; ++k) {
+    check_hip(ana::launch_ttt_chain(u32p(fs[0]), u32p(fs[1]), u32p(bs[0]), u32p(bs[1]), n, (int)K, P, tau2,
+                                    msg.data_ptr<double>(), prior.data_ptr<double>(), fwd.data_ptr<double>(),
+                                    cav.data_ptr<double>(), mu64.data_ptr<double>(), out.data_ptr<float>(),
+                                    edges.data_ptr<uint8_t>(), k > 0 ? 1 : 0,
+                                    reinterpret_cast<uint64_t*>(bits.data_ptr<int64_t>()) + k, s),
+              "ttt_chain");
+    if (k == sweeps) break;
+    if (k > 0 && tol >= 0.0 && bits[k].view(torch::kFloat64).item<double>() < tol) break;
+    check_hip(ana::launch_ttt_match((int)K, rec.data_ptr<int32_t>(), M, P, u32p(mword), cav.data_ptr<double>(),
+                                    msg.data_ptr<double>(), beta2, damping, s),
+              "ttt_match");
+    ++run;
+  }
+  return {out, bits.narrow(0, 1, run).view(torch::kFloat64), cav, msg, counters.to(torch::kInt64)};
+}
+
 // adds the predictions of one window's priors to the scorecard table [6, 33, 4] int64 in
 // place; returns the pred rows [M, 4] int32 (flags word, p_win0 bits, p_outcome bits, 0) when
 // ``keep``, else an empty tensor
@@ -1756,6 +1843,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("carry"), py::arg("rec"), py::arg("rows"), py::arg("tau"), py::arg("track"), py::arg("mode"));
   m.attr("HINDSIGHT_TILE") = ana::kHindsightTile;
   m.attr("HINDSIGHT_BUDGET_C") = ana::kHsBudgetC;
+  m.def("ttt_fit", &ttt_fit, "K20: [out [M, 2K, 2] fp32, residual fp64 [sweeps run], cav [M * 2K, 2] fp64, msg [M * 2K, 2] "
+        "fp64, counters int64 [3] (bad, flat, inconsistent)] -- one history (rec [M, 2K+2] joined with its packed rows "
+        "[M, W] and its K14 priors [M, 4, 2K]) re-estimated jointly by expectation propagation: ttt_fit(rec, rows, "
+        "priors, attrs, vst, P, beta2, tau, unknown_sigma, track, mode, sweeps, tol, damping); tol < 0: no early stop",
+        py::arg("rec"), py::arg("rows"), py::arg("priors"), py::arg("attrs"), py::arg("vst"), py::arg("P"),
+        py::arg("beta2"), py::arg("tau"), py::arg("unknown_sigma"), py::arg("track"), py::arg("mode"),
+        py::arg("sweeps"), py::arg("tol"), py::arg("damping"));
+  m.attr("TTT_TILE") = ana::kTttTile;
   m.def("score_add", &score_add, "K14: add the predictions of a window's priors to the scorecard table [6, 33, 4] int64 "
         "in place; returns the pred rows [M, 4] int32 when keep: score_add(table, rec, priors, rows, attrs, vst, P, "
         "beta2, unknown_sigma, track, modes, keep)",

@@ -13,7 +13,8 @@
 //
 // It conditions on the filtered posteriors; it does not run the match factors again, so it is
 // not TrueSkill-Through-Time: what a later match says about a player reaches an earlier one
-// only through that player's own chain, never through the team mates and opponents.
+// only through that player's own chain, never through the team mates and opponents.  K20
+// (ttt_core.h) is that; it shares the elements below and with zero sweeps computes the same.
 //
 // Elements.  A slot is an element when it is live (score_core.h prior_live_mask), its row's
 // status is kRated, no later slot of the record carries the same player (prior_last_mask) and,

@@ -24,6 +24,7 @@
 #include "rate_core.h"
 #include "score_core.h"
 #include "select_core.h"
+#include "ttt_core.h"
 
 namespace ana {
 
@@ -772,6 +773,121 @@ int host_hindsight_add(int K, const int32_t* rec, const float* rows, int64_t W, 
   return with_team_size(K, [&](auto k) {
     hindsight_add_k<decltype(k)::value>(rec, rows, W, M, P, tau2, track, mode, carry, out, bad);
   }) ? 0 : -1;
+}
+
+// K20: the schedule of ttt.hip as loops.  A chain is walked forwards and backwards by the
+// recursions of ttt_core.h themselves; the device composes scan elements instead.
+template <int K>
+static int64_t ttt_fit_k(const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, const float* priors,
+                         const float* attrs, const float* vst, float us, double beta2, double q, int track, int mode,
+                         int64_t sweeps, double tol, double theta, float* out, double* cav, double* msg,
+                         double* resid, int64_t* counters) {
+  constexpr int S = 2 * K;
+  const int64_t n = M * S;
+  std::vector<uint32_t> mword((size_t)M);
+  std::vector<double> prior((size_t)(2 * n)), fwd((size_t)(2 * n)), mu64((size_t)n);
+  std::vector<int64_t> start((size_t)P + 2, 0);
+  int32_t cnt[kTttCounters] = {0, 0, 0};
+  for (int64_t i = 0; i < 2 * n; ++i) {
+    out[i] = NAN;
+    cav[i] = msg[i] = 0.0;
+  }
+  for (int64_t m = 0; m < M; ++m) {
+    const int32_t* r = rec + m * (S + 2);
+    uint32_t row[5 * S + 2];
+    memcpy(row, rows + m * W, sizeof(row));
+    float mu[S], sg[S];
+    memcpy(mu, row + (track == kHsMode ? 3 * S : 0), sizeof(mu));
+    memcpy(sg, row + (track == kHsMode ? 4 * S : S), sizeof(sg));
+    mword[m] = ttt_setup_match<K>(r, P, select_row_status<K>(row), priors + m * (4 * S), mu, sg, attrs, vst, us, track,
+                                  mode, q, cnt, [&](int j, double h, double pi, double m_pre, double v_pre) {
+                                    const int64_t i = m * S + j;
+                                    msg[2 * i] = h;
+                                    msg[2 * i + 1] = pi;
+                                    prior[2 * i] = m_pre;
+                                    prior[2 * i + 1] = v_pre;
+                                    ++start[(size_t)r[j] + 2];
+                                  });
+  }
+  for (int c = 0; c < kTttCounters; ++c) counters[c] += cnt[c];
+  // every player's elements in chronological order: order[start[p + 1] ...) once filled
+  for (int64_t p = 0; p < P; ++p) start[(size_t)p + 2] += start[(size_t)p + 1];
+  std::vector<int64_t> order((size_t)start[(size_t)P + 1]);
+  for (int64_t m = 0; m < M; ++m)
+    for (int j = 0; j < S; ++j)
+      if ((mword[m] >> j) & 1u) order[(size_t)start[(size_t)rec[m * (S + 2) + j] + 1]++] = m * S + j;
+  // now start[p + 1] is the end of p's chain and start[p] its begin
+  auto chain_pass = [&](bool have_before) {
+    double worst = 0.0;
+    for (int64_t p = 0; p < P; ++p) {
+      const int64_t a = start[(size_t)p], b = start[(size_t)p + 1];
+      if (a == b) continue;
+      double fm = prior[2 * order[a]], fv = prior[2 * order[a] + 1];
+      for (int64_t t = a; t < b; ++t) {
+        const int64_t i = order[t];
+        fwd[2 * i] = fm;
+        fwd[2 * i + 1] = fv;
+        const double pi = 1.0 / fv + msg[2 * i + 1], h = fm / fv + msg[2 * i];
+        fm = h / pi;
+        fv = 1.0 / pi + q;
+      }
+      double hb = 0.0, pib = 0.0;
+      for (int64_t t = b - 1; t >= a; --t) {
+        const int64_t i = order[t];
+        double mu, var;
+        ttt_beliefs(fwd[2 * i], fwd[2 * i + 1], hb, pib, msg[2 * i], msg[2 * i + 1], cav[2 * i], cav[2 * i + 1], mu,
+                    var);
+        out[2 * i] = (float)mu;
+        out[2 * i + 1] = (float)sqrt(var);
+        if (have_before) worst = fmax(worst, fabs(mu - mu64[i]));
+        mu64[i] = mu;
+        const double hs = hb + msg[2 * i], ps = pib + msg[2 * i + 1], w = 1.0 + q * ps;
+        hb = hs / w;
+        pib = ps / w;
+      }
+    }
+    return worst;
+  };
+  // Jacobi: a factor reads the cavities of the chain pass before and, to damp, its own old messages
+  int64_t run = 0;
+  for (int64_t k = 0;; ++k) {
+    const double r = chain_pass(k > 0);
+    if (k > 0) resid[k - 1] = r;
+    if (k == sweeps || (k > 0 && tol >= 0.0 && r < tol)) break;
+    for (int64_t m = 0; m < M; ++m) {
+      if (!(mword[m] & kTttActive)) continue;
+      ttt_match_factor<K>(
+          rec + m * (S + 2), P, mword[m] & ~kTttActive, beta2,
+          [&](int j, double& mu_c, double& s2) {
+            mu_c = cav[2 * (m * S + j)];
+            s2 = cav[2 * (m * S + j) + 1];
+          },
+          [&](int j, double h, double pi) {
+            const int64_t i = m * S + j;
+            msg[2 * i] = ttt_damp(msg[2 * i], h, theta);
+            msg[2 * i + 1] = ttt_damp(msg[2 * i + 1], pi, theta);
+          });
+    }
+    ++run;
+  }
+  return run;
+}
+
+int64_t host_ttt_fit(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P,
+                     const float* priors, const float* attrs, const float* vst, float unknown_sigma, double beta2,
+                     double tau2, int track, int mode, int64_t sweeps, double tol, double theta, float* out,
+                     double* cav, double* msg, double* resid, int64_t* counters) {
+  if (!window_slots_ok(K, W, M, P) || !(tau2 >= 0.0) || !std::isfinite(tau2) || !(beta2 >= 0.0) ||
+      !std::isfinite(beta2) || (track != kHsShared && track != kHsMode) ||
+      (track == kHsMode && (mode < 0 || mode >= kModes)) || sweeps < 0 || !(theta > 0.0 && theta <= 1.0) ||
+      vst == nullptr)
+    return -1;
+  int64_t run = -1;
+  with_team_size(K, [&](auto k) {
+    run = ttt_fit_k<decltype(k)::value>(rec, rows, W, M, P, priors, attrs, vst, unknown_sigma, beta2, tau2, track,
+                                        mode, sweeps, tol, theta, out, cav, msg, resid, counters);
+  });
+  return run;
 }
 
 // K14: the prediction of every match from its priors, on preview's fp64 path, and its score

@@ -92,6 +92,18 @@ void host_pairs_merge(const int64_t* keys, const int32_t* counts, int64_t n, Pai
 // out [M][2K][2] fp32 (NaN where no element); *bad is incremented.  -1: bad arguments.
 int host_hindsight_add(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P, double tau2,
                        int track, int mode, double* carry, float* out, int64_t* bad);
+// K20 host mirror (ttt_core.h): the same schedule as plain loops -- per chain the forward and
+// backward recursions themselves, not the composition of scan elements the device runs -- over
+// rec [M][2K+2] joined with rows [M][W] and the K14 priors [M][4][2K].  Runs at most `sweeps`
+// sweeps (a chain pass, then the match factors) and a final chain pass; stops early after the
+// chain pass whose residual is < tol (tol < 0: never).  out [M][2K][2] fp32 (NaN where no
+// element), cav and msg [M * 2K][2] fp64 (the cavities of the last chain pass and the messages it
+// ran on), resid [sweeps], counters [3] (bad, flat, inconsistent).  Returns the sweeps run, -1:
+// bad arguments.
+int64_t host_ttt_fit(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P,
+                     const float* priors, const float* attrs, const float* vst, float unknown_sigma, double beta2,
+                     double tau2, int track, int mode, int64_t sweeps, double tol, double theta, float* out,
+                     double* cav, double* msg, double* resid, int64_t* counters);
 // K17 host mirror (profile_core.h): the games of rec [M][2K+2] joined with rows [M][W] and stats
 // [M][2K][8], each added to its row of table [P][kProfileWords] and its cell of cells
 // [profile_table_words(n_edges + 1)], bit-identical to the device.  -1: bad arguments.

@@ -183,6 +183,31 @@ int launch_hindsight_keys(int K, const int32_t* rec, const float* rows, int64_t 
 int launch_hindsight_scan(const uint32_t* keys, const uint32_t* vals, const uint32_t* events, int64_t n, int K,
                           int64_t P, double tau2, double* carry, void* edges, float* out, hipStream_t s);
 
+// K20 through time (ttt.hip, ttt_core.h): the joint re-estimate of one history rec [M][2K+2]
+// joined with its packed rows [M][W] (alignment as for K10) and its K14 priors [M][4][2K] fp32
+// (16-B aligned), M * 2K = n <= kMaxSlots.  track, mode as K16.  Per slot buffers, [n] each: msg,
+// prior, fwd, cav (2 fp64, 16-B aligned), mu64 (fp64), out (2 fp32, 8-B aligned); mword [M];
+// counters [kTttCounters] int32 (bad, flat, inconsistent; added to).  ttt_setup fills the sort
+// pairs of the forward scan (keys_f, vals_f: slot i at i) and of the backward scan (keys_b,
+// vals_b: slot i at n - 1 - i), msg, prior, mword, the NaNs of out and the counters; both pair
+// sets are sorted with launch_radix_sort_pairs on bit_length(P) bits.  ttt_chain is one chain
+// pass over the sorted pairs: it fills fwd, cav, out and mu64 and, when have_before, folds the
+// largest |mu - mu64 of the pass before| into *resid (the bits of a non-negative fp64, integer
+// max; 8-B aligned; edges: ttt_edge_bytes(n) bytes, 8-B aligned).  ttt_match runs the match
+// factors: it reads cav and writes msg, damped by theta in (0, 1].  Everything is stream-ordered.
+constexpr int kTttTile = 4096;  // sorted elements per workgroup of the scans
+size_t ttt_edge_bytes(int64_t n);
+int launch_ttt_setup(int K, const int32_t* rec, const float* rows, int64_t W, int64_t M, int64_t P,
+                     const float* priors, const float* attrs, const float* vst, float unknown_sigma, int track,
+                     int mode, double tau2, uint32_t* keys_f, uint32_t* vals_f, uint32_t* keys_b, uint32_t* vals_b,
+                     double* msg, double* prior, float* out, uint32_t* mword, int32_t* counters, hipStream_t s);
+int launch_ttt_chain(const uint32_t* keys_f, const uint32_t* vals_f, const uint32_t* keys_b, const uint32_t* vals_b,
+                     int64_t n, int K, int64_t P, double tau2, const double* msg, const double* prior, double* fwd,
+                     double* cav, double* mu64, float* out, void* edges, int have_before, uint64_t* resid,
+                     hipStream_t s);
+int launch_ttt_match(int K, const int32_t* rec, int64_t M, int64_t P, const uint32_t* mword, const double* cav,
+                     double* msg, double beta2, double theta, hipStream_t s);
+
 // K17 profiles (profile.hip, profile_core.h): one window rec [M][2K+2] joined with its packed rows
 // [M][W] (alignment as for K10) and its stat vectors stats [M][2K][8] fp32 (16-B aligned), M * 2K
 // <= kMaxSlots.  profile_keys writes per slot i = m * 2K + j the sort key (the player of a game,

@@ -8,5 +8,6 @@ from .profiles import ProfileTable  # noqa: F401
 from .matchmake import (Balanced, Preview, balance_lobbies, fill_winners, make_lobbies,  # noqa: F401
                         preview_matches)
 from .hindsight import Hindsight  # noqa: F401
+from .through_time import ThroughTime  # noqa: F401
 from .islands import Islands  # noqa: F401
 from .expectations import Expectations  # noqa: F401

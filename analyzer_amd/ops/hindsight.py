@@ -13,7 +13,8 @@ newest one (which is its own smoothed value),
 This is the Rauch-Tung-Striebel smoother of each player's own chain, conditional on the
 filtered posteriors.  It is **not** TrueSkill-Through-Time: the match factors are not run
 again, so a later match tells an earlier one only what it told the player's own track, and
-nothing through team mates and opponents.
+nothing through team mates and opponents.  ``ThroughTime`` (K20, ``ops/through_time.py``) is
+that; with zero sweeps it returns what this returns.
 
     hs = Hindsight(P, device)                       # or track="ranked", ...
     sm = hs.add(rec, rows)                          # windows NEWEST FIRST; fp32 [M, 2K, 2]

@@ -37,6 +37,9 @@ for K = 4, 5).  ``records="resident"`` keeps them where the executor writes them
 * ``hindsight(num_players, rec_of, players)`` smooths every player's skill curve backwards
   over the filled windows (``ops/hindsight.py`` ``Hindsight``, csrc/hindsight.hip, K16) and
   returns the filtered and the smoothed curve of the listed players.  One rank only.
+* ``through_time(roster0, rec_of, players)`` re-estimates the whole history jointly
+  (``ops/through_time.py`` ``ThroughTime``, csrc/ttt.hip, K20) -- every match factor run again
+  against everyone's smoothed belief -- and returns the listed players' curves.  One rank only.
 * ``export`` / ``load`` move the filled rows through two pinned slots on a copy stream
   into one flat file plus a small JSON header; the round trip is bit-identical.  This
   is how an arena is persisted: checkpoints do not hold arena rows, so a resumed run
@@ -61,6 +64,7 @@ from ..ops.native import native
 from ..ops.pairs import PairTable
 from ..ops.rate import RateResult, Roster
 from ..ops.scorecard import Scorecard
+from ..ops.through_time import ThroughTime
 
 # an arena fits when, beside the roster, it leaves at least this fraction of the device's
 # total memory free (the executor's workspaces, the next windows' records and schedules, the
@@ -318,6 +322,49 @@ class RecordArena:
             dt = (torch.int64, torch.int32, torch.int32) + (torch.float32,) * 4
             return {n: torch.empty(0, dtype=d, device=self.device) for n, d in zip(names, dt)}
         return {n: torch.cat([p[i] for p in parts]) for i, n in enumerate(names)}
+
+    def through_time(self, roster0, rec_of: Callable[[int, int], torch.Tensor], players: Sequence[int],
+                     sweeps: int = 8, tol: Optional[float] = None, damping: float = 1.0,
+                     **kw) -> Dict[str, torch.Tensor]:
+        """The filtered curve of ``players`` and their curve re-estimated jointly through time
+        (``ops/through_time.py`` ``ThroughTime``, K20) over the filled windows, which are
+        joined into one history: a fit takes the whole of it, so above the slot limit of one
+        fit this raises ``ValueError``.  ``roster0``: the roster the arena's history starts
+        from, as for ``scorecard``; ``sweeps``, ``tol``, ``damping`` of ``ThroughTime.fit``;
+        ``kw``: ``track``, ``cfg``.  Columnar tensors in chronological order as ``hindsight``
+        returns them, with ``mu_tt``, ``sigma_tt`` for the smoothed pair; ``residual`` and
+        ``sweeps`` of the fit ride along as a fp64 tensor.  One rank only."""
+        if self.size > 1:
+            raise ValueError("through time chains the whole history: it needs a one-rank arena, this is rank %d of "
+                             "%d" % (self.rank, self.size))
+        num_players = int((roster0.state if hasattr(roster0, "state") else roster0).shape[0])
+        tt = ThroughTime(roster0, **kw)
+        mu_name, sigma_name = ("s_mu", "s_sig") if tt.track == SHARED else ("m_mu", "m_sig")
+        names = ("match", "player", "slot", "mu", "sigma", "mu_tt", "sigma_tt")
+        spans = list(self.windows())
+        slots = sum(hi - lo for lo, hi in spans) * 2 * self.K
+        if slots > tt.max_slots:
+            raise ValueError("the arena holds %d slots, above the limit of %d slots (MAX_SLOTS) of one fit"
+                             % (slots, tt.max_slots))
+        if not spans:
+            dt = (torch.int64, torch.int32, torch.int32) + (torch.float32,) * 4
+            out = {n: torch.empty(0, dtype=d, device=self.device) for n, d in zip(names, dt)}
+            out["residual"] = torch.empty(0, dtype=torch.float64)
+            return out
+        first = spans[0][0]
+        rec = torch.cat([rec_of(lo, hi) for lo, hi in spans])
+        rows = torch.cat([self.rows[int(self.local_row(lo)):int(self.local_row(lo)) + hi - lo] for lo, hi in spans]) \
+            if len(spans) > 1 else self.rows[int(self.local_row(first)):int(self.local_row(first)) + spans[0][1] - first]
+        fit = tt.fit(rec, rows, sweeps=sweeps, tol=tol, damping=damping)
+        cols = hits_columns(records_select(rec, rows, first, num_players,
+                                           player_bitmap(players, num_players, self.device)))
+        at = (cols["match"] - first) * (2 * self.K) + cols["slot"].to(torch.int64)
+        pair = fit.smoothed.reshape(-1, 2).index_select(0, at)
+        keep = ~torch.isnan(pair[:, 1])  # the hits that are elements of the track
+        out = dict(zip(names, (cols["match"][keep], cols["player"][keep], cols["slot"][keep], cols[mu_name][keep],
+                               cols[sigma_name][keep], pair[keep, 0], pair[keep, 1])))
+        out["residual"] = torch.tensor(fit.residual, dtype=torch.float64)
+        return out
 
     # ------------------------------------------------------------ sizing
     @staticmethod

@@ -48,8 +48,10 @@ streams a long synthetic history through the engine window by window:
         --window 16000000 --records resident --pairs 17,4242  # whom they play with and against (ops/pairs.py)
     python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
         --window 16000000 --records resident --hindsight 17,4242 --hindsight-track ranked  # smoothed curves (ops/hindsight.py)
+    python -m analyzer_amd.runtime.rerate --matches 20000000 --players 1000000 \\
+        --window 16000000 --records resident --through-time 17,4242 --through-time-sweeps 12  # the joint re-estimate (ops/through_time.py)
     python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
-        --window 16000000 --records resident --islands --islands-ranks 8  # which ratings are comparable (ops/islands.py)
+        --window 16000000 --records resident --islands --islands-ranks 8 # which ratings are comparable (ops/islands.py)
     python -m analyzer_amd.runtime.rerate --matches 500000000 --players 10000000 \\
         --window 16000000 --records resident --expect 17,4242 --expect-outliers 20  # wins against the odds (ops/expectations.py)
 """
@@ -452,6 +454,22 @@ def hindsight_lines(curves: dict, ids, track: str) -> list:
     return lines
 
 
+def through_time_lines(curves: dict, ids, track: str) -> list:
+    """One JSON-ready dict per player of ``ids`` from a ``RecordArena.through_time`` result: the
+    matches of the player's chain with the filtered and the jointly re-estimated (mu, sigma) at
+    each, and the fit's sweeps and last residual."""
+    resid = curves["residual"].tolist()
+    lines = []
+    for p in ids:
+        sel = (curves["player"] == p).nonzero().reshape(-1)
+        line = {"through_time": int(p), "track": track, "records": int(sel.numel()), "sweeps": len(resid),
+                "residual": _num(resid[-1]) if resid else None}
+        for name in ("match", "mu", "sigma", "mu_tt", "sigma_tt"):
+            line[name] = [_num(v) for v in curves[name].index_select(0, sel).cpu().tolist()]
+        lines.append(line)
+    return lines
+
+
 def pair_lines(table, ids, top: int = 5) -> list:
     """One JSON-ready dict per player of ``ids`` from a ``PairTable`` (ops/pairs.py): the number
     of distinct players it shared a rated match with, and its ``top`` most frequent team mates
@@ -550,6 +568,14 @@ def main(argv=None) -> int:
                          "matches, not a re-run of the match factors")
     ap.add_argument("--hindsight-track", default=None, metavar="TRACK",
                     help="with --hindsight: the shared track (default) or a mode's")
+    ap.add_argument("--through-time", default=None, metavar="ID[,ID...]",
+                    help="with --records resident: print each player's filtered skill curve and the curve "
+                         "re-estimated jointly through time after the run (JSON lines; one rank only): every match "
+                         "factor is run again against everyone's smoothed belief (TrueSkill-Through-Time)")
+    ap.add_argument("--through-time-sweeps", type=int, default=None, metavar="N",
+                    help="with --through-time: sweeps over the history (default 8)")
+    ap.add_argument("--through-time-track", default=None, metavar="TRACK",
+                    help="with --through-time: the shared track (default) or a mode's")
     ap.add_argument("--pairs", default=None, metavar="ID[,ID...]",
                     help="with --records resident: print whom each player played with and against after the run "
                          "(JSON lines): the distinct partners and the most frequent team mates and opponents")
@@ -628,6 +654,23 @@ def main(argv=None) -> int:
         ap.error("--hindsight: %s" % e)
     if any(p < 0 or p >= spec.players for p in hindsight_ids):
         ap.error("--hindsight ids must lie in [0, %d)" % spec.players)
+    if args.through_time and not resident:
+        ap.error("--through-time needs --records resident")
+    if (args.through_time_track or args.through_time_sweeps is not None) and not args.through_time:
+        ap.error("--through-time-track and --through-time-sweeps need --through-time")
+    if args.through_time and size > 1:
+        ap.error("--through-time chains the whole history: it runs on one rank")
+    tt_track = args.through_time_track or "shared"
+    tt_sweeps = 8 if args.through_time_sweeps is None else args.through_time_sweeps
+    try:
+        tt_ids = [int(p) for p in (args.through_time or "").split(",") if p.strip()]
+        track_of(tt_track)
+        if tt_sweeps < 0:
+            raise ValueError("sweeps must be >= 0, got %d" % tt_sweeps)
+    except ValueError as e:
+        ap.error("--through-time: %s" % e)
+    if any(p < 0 or p >= spec.players for p in tt_ids):
+        ap.error("--through-time ids must lie in [0, %d)" % spec.players)
     if args.pairs and not resident:
         ap.error("--pairs needs --records resident")
     if (args.pairs_modes or args.pairs_top is not None) and not args.pairs:
@@ -722,7 +765,7 @@ def main(argv=None) -> int:
                          plan["reserve_bytes"]), file=sys.stderr, flush=True)
                 return 2
             roster0 = None
-            if args.score or expect_ids:
+            if args.score or expect_ids or tt_ids:
                 roster0 = start_roster(spec, args.checkpoint_dir, torch.device(args.device or dev))
             res, roster, arena = rerate_resident(spec, args.device or dev, args.checkpoint_dir, plan=plan,
                                                  checkpoint_every=args.checkpoint_every,
@@ -770,6 +813,11 @@ def main(argv=None) -> int:
         curves = arena.hindsight(spec.players, stream_records(spec, arena.device), hindsight_ids,
                                  track=hindsight_track)
         for line in hindsight_lines(curves, hindsight_ids, hindsight_track):
+            print(json.dumps(line), flush=True)
+    if tt_ids:
+        curves = arena.through_time(roster0, stream_records(spec, arena.device), tt_ids, sweeps=tt_sweeps,
+                                    track=tt_track)
+        for line in through_time_lines(curves, tt_ids, tt_track):
             print(json.dumps(line), flush=True)
     if args.islands:
         isl = arena.islands(spec.players, stream_records(spec, arena.device), modes=island_modes)  # this rank's blocks
